@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: ray-bounces/s (+ convolved audio frames/s) on the conference scene.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs with --dump-outputs
+(DIR/ir_left.npy, ir_right.npy, conv_left.npy, conv_right.npy, float32) and prints the result line.
+With --full the legs beside the headline follow (single-frame and per-launch kernel times, rooflines
+against the stored profiles, input reuse, host buffers, the C5 moving listener, streaming, the CPU
+baseline) and the line carries their fields too.
 
 One step = one pass of the hot path on every GPU (BASELINE.json configs[2], per GPU):
   trace this GPU's 1M-ray shard x 16 bounces (fused HIP kernel) -> one RCCL all-reduce (int64
@@ -507,9 +513,50 @@ def _stdout_to_stderr():
         os.close(saved)
 
 
+def leg_steps(steps: int, ring: int) -> int:
+    """Steps of a --full leg that reads per-launch times back: the timed steps may outnumber the
+    renderer's timing ring (they record no events), such a leg keeps to the launches the ring holds."""
+    return min(steps, ring)
+
+
+def dump_outputs(path: str, g, bufs, own, frames: int, rank: int, whole_file: bool) -> None:
+    """What the last timed step left for a caller of the hot path, as float32 .npy files: the stereo
+    IR (ir_left, ir_right: the all-reduced IR every rank holds, written by rank 0) and the convolved
+    file (conv_left, conv_right).  One process writes the whole convolved file (its members' shards
+    put together); a rank of a multi-process job writes the frames it owns as conv_*_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    if rank == 0:
+        for name, a in zip(("ir_left", "ir_right"), g.get_ir()):
+            np.save(os.path.join(path, name + ".npy"), np.asarray(a, np.float32))
+    local = len(bufs) == g.n_ranks  # every rank of the group lives in this process
+    for ch, name in ((1, "conv_left"), (2, "conv_right")):
+        if whole_file:  # every member holds the whole convolved file: the first one's
+            out = bufs[0][ch].to_numpy(np.float32, frames)
+        else:
+            out = np.zeros(frames, np.float32)
+            for b, (lo, hi) in zip(bufs, own):
+                out[lo:hi] = b[ch].to_numpy(np.float32, frames)[lo:hi]
+        if local:
+            np.save(os.path.join(path, name + ".npy"), out)
+        elif whole_file:
+            if rank == 0:
+                np.save(os.path.join(path, name + ".npy"), out)
+        else:
+            np.save(os.path.join(path, f"{name}_rank{rank}.npy"), out[own[0][0]:own[0][1]])
+
+
 # -------------------------------------------------------------------------------------- main ---
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other leg too (single-frame and per-launch kernel times, "
+                         "rooflines against the stored profiles, input reuse, host buffers, the C5 moving listener, "
+                         "streaming, the CPU baseline) and report them in the line; a plain run only sets up, warms "
+                         "up, times the steps and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR as float32 .npy files: "
+                         "ir_left, ir_right (the stereo IR) and conv_left, conv_right (the convolved file); the "
+                         "inputs are the same for the same arguments, so two builds compare output for output")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
@@ -574,8 +621,12 @@ def main(argv=None) -> int:
     from audiorenderingv2_amd.scene import CONFERENCE_EMITTER, CONFERENCE_LISTENER, reference_audio
 
     ring = int(lib().arx_timing_ring())
-    if args.steps < 1 or args.steps > ring:
-        raise SystemExit(f"bench.py: --steps must be in [1, {ring}] (the renderer's per-launch timing ring)")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
+    if args.timing_events and args.steps > ring:
+        raise SystemExit(f"bench.py: --steps must be in [1, {ring}] with --timing-events (the renderer's per-launch "
+                         "timing ring)")
+    k_leg = leg_steps(args.steps, ring)
     have = device_count()
     if have < plan["local_gpus_needed"]:
         raise SystemExit(f"bench.py: --gpus {args.gpus} needs {plan['local_gpus_needed']} visible GPU(s) in this "
@@ -694,6 +745,93 @@ def main(argv=None) -> int:
     st0 = m0.stats()
     q_m0 = int(st0["queries"])
     value = q_all * args.steps / elapsed
+    if args.dump_outputs:  # the last timed step's IR and convolved file, before any other leg runs
+        wd.beat("dump_outputs")
+        dump_outputs(args.dump_outputs, g, bufs, own, frames, rank, not (sharded_conv and conv_plan_shards))
+        wd.beat()
+    n_tris = int(stats["n_scene_tris"] + stats["n_receiver_tris"])
+    # unique stereo frames: the file once per step when it is time-block sharded (or on one GPU), every
+    # GPU's copy with --replicated-convolution
+    conv_frames_step = unique_frames * args.steps / elapsed  # the pipeline: frames convolved per timed step
+    result = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "ray-bounces/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if wl.get("total") else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic: deterministic conference.obj stand-in (seed 42; conference.obj is missing from the "
+                "reference checkout) + the reference's own audio (" + wl["audio"] + ", channel 0)",
+        "full": bool(args.full),
+        "config": {
+            "workload": wl["desc"],
+            "scene_triangles": n_tris,
+            "rays_per_gpu": total_rays // world,
+            "max_bounces": wl["max_bounces"],
+            "sample_rate": wl["sample_rate"],
+            "ir_len": ir_len,
+            "audio_frames": frames,
+            "convolution": ("one GPU: the whole file" if world == 1 else
+                            (f"time-block sharded over {world} GPUs (arx_group_convolute_device): rank r owns the "
+                             f"output frames of block pairs [r P/{world}, (r+1) P/{world}) and re-makes its seam pair, "
+                             "no collective" if conv_plan_shards else
+                             "this plan has no chained pass: every GPU convolves the whole file")
+                            if sharded_conv else f"replicas: each of the {world} GPUs convolves the whole file"),
+            "convolved_frames_per_step": unique_frames,
+            "conv_frames_owned_rank0": [int(own[0][0]), int(own[0][1])],
+            "frames_in_flight": args.frames_in_flight,
+            # the persistent trace grid (arx_stats.trace_grid_cus): half the CUs' wave slots per launch
+            # with frames in flight, so two frames' launches run side by side; the full device with one
+            # (--full adds the kernel-times leg's grid beside it)
+            "trace_grid_cus": {"timed_steps": int(st0["trace_grid_cus"])},
+            "parallelism": (f"ray-shard x{world}, "
+                            + ("REHEARSAL (--debug-oversubscribe): the ranks' histograms summed on device 0, no RCCL"
+                               if args.debug_oversubscribe else
+                               "native RCCL int64 IR all-reduce per step" if world > 1 else
+                               "one rank: the group's RCCL communicator exists but arx_group_render skips its no-op "
+                               "IR all-reduce (arx_group.cpp; tests/test_gpu_collectives.py forces it on one GPU)")
+                            + " (arx_group: "
+                            + ("one process, ncclCommInitAll over devices " + ",".join(map(str, plan["devices"]))
+                               if plan["mode"] == "local" and not args.debug_oversubscribe else
+                               "one process, device 0 listed " + str(world) + " times" if args.debug_oversubscribe
+                               else f"one process per GPU, ncclCommInitRank, rank {rank}")
+                            + ")"),
+        },
+        "runtime": runtime_info(),
+        "collectives_issued": dict(collectives, forced=bool(args.debug_force_collectives),
+                                   note="RCCL collectives the headline group issued up to the end of the timed steps "
+                                        "(a one-rank group skips them unless forced)"),
+        "setup_s_rank0": setup_s,
+        "preroll": {"steps": pre_steps, "seconds_rank0": preroll_s,
+                    "why": "untimed steps before the W warmup steps, until the GPU runs at its sustained clock "
+                           "(a fresh or idle MI355X ramps over its first ~10 C3 launches, 2.95 -> 2.67 ms; "
+                           "profiles/r04/trace_ramp.json)"},
+        "ray_bounces_per_step": q_all,
+        "nominal_ray_bounces_per_s": total_rays * wl["max_bounces"] * args.steps / elapsed,
+        "receiver_hits_per_step_rank0": int(st0["receiver_hits"]),
+        "convolved_frames_per_s": conv_frames_step,
+    }
+    if args.dump_outputs:
+        result["dumped_outputs"] = args.dump_outputs  # as given
+
+    def finish() -> int:
+        wd.disarm()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        for b in bufs:
+            for x in b:
+                x.close()
+        ranks.barrier()
+        g.close()
+        return 0
+
+    if not args.full:
+        return finish()
     # With two frames in flight a launch's HIP-event window (on its stream) also holds the time it
     # queues behind the other frame's kernels, so the per-launch times (phases, rooflines) come from
     # a single-frame leg: the same group, W + K steps with one frame in flight.
@@ -706,13 +844,13 @@ def main(argv=None) -> int:
         sync()
         ranks.barrier()
         t0s = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k_leg):
             step()
         sync()
         ranks.barrier()
         el1 = ranks.max(time.perf_counter() - t0s)
         q1 = int(round(ranks.sum(int(g.stats()["queries"]))))
-        single_frame = {"value": q1 * args.steps / el1, "ms_per_step": el1 / args.steps * 1e3,
+        single_frame = {"value": q1 * k_leg / el1, "ms_per_step": el1 / k_leg * 1e3,
                         "why": "the same steps with one frame in flight (no per-launch timing events, as in the "
                                "timed steps)"}
     # The per-launch kernel times: W + K more single-frame steps with the timing events on (HIP
@@ -726,19 +864,19 @@ def main(argv=None) -> int:
     sync()
     ranks.barrier()
     t0k = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(k_leg):
         step()
     sync()
     ranks.barrier()
-    timed_leg_ms = ranks.max(time.perf_counter() - t0k) / args.steps * 1e3
-    trace_list = m0.trace_times(args.steps)
-    assert len(trace_list) == args.steps, (len(trace_list), args.steps)
+    timed_leg_ms = ranks.max(time.perf_counter() - t0k) / k_leg * 1e3
+    trace_list = m0.trace_times(k_leg)
+    assert len(trace_list) == k_leg, (len(trace_list), k_leg)
     grid_cus_single = int(m0.stats()["trace_grid_cus"])
     trace_ms = float(np.mean(trace_list))
     # the histogram all-reduce's own window (HIP events on each member's stream around the RCCL call,
     # arx_group_allreduce_times), the slowest member, max over ranks; none at one rank unless forced
-    ar_lists = [g.allreduce_times(args.steps, i) for i in range(len(members))]
-    if all(len(a) == args.steps for a in ar_lists):
+    ar_lists = [g.allreduce_times(k_leg, i) for i in range(len(members))]
+    if all(len(a) == k_leg for a in ar_lists):
         allreduce_ms = ranks.max(max(float(np.mean(a)) for a in ar_lists))
         allreduce_why = (f"RCCL int64 all-reduce of 2 x {ir_len} bins over {world} rank(s): HIP events around the "
                          "collective on each member's stream (arx_group_allreduce_times), mean of the K timed "
@@ -748,8 +886,8 @@ def main(argv=None) -> int:
         allreduce_why = "one rank: arx_group_render skips the no-op all-reduce (--debug-force-collectives times it)"
     conv_ms_all = []
     for m in members:
-        cl = m.conv_times(args.steps)
-        assert len(cl) == args.steps, (len(cl), args.steps)
+        cl = m.conv_times(k_leg)
+        assert len(cl) == k_leg, (len(cl), k_leg)
         conv_ms_all.append(float(np.mean(cl)))
     conv_ms = conv_ms_all[0]
     # the frames rank 0's convolution window covers: its shard, or the whole file
@@ -776,14 +914,14 @@ def main(argv=None) -> int:
         sync()
         ranks.barrier()
         t0r = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k_leg):
             step_reuse()
             wd.beat()
         sync()
         ranks.barrier()
         elr = ranks.max(time.perf_counter() - t0r)
-        reuse_ms = float(np.mean(m0.conv_times(args.steps)))
-        reuse = {"conv_ms_rank0": reuse_ms, "ms_per_step": elr / args.steps * 1e3,
+        reuse_ms = float(np.mean(m0.conv_times(k_leg)))
+        reuse = {"conv_ms_rank0": reuse_ms, "ms_per_step": elr / k_leg * 1e3,
                  "convolved_frames_per_s_kernel_window": frames / (reuse_ms * 1e-3),
                  "why": "the reference's re-render pattern (the same file, a new IR every frame): the file's blocks "
                         "transformed once (arx_convolute_prepare_input), each step's convolution "
@@ -808,14 +946,14 @@ def main(argv=None) -> int:
         ranks.barrier()
         t0h = time.perf_counter()
         host_conv = []
-        for _ in range(args.steps):
+        for _ in range(k_leg):
             host_conv.append(max(step_host()))
             wd.beat()
         sync()
         ranks.barrier()
         elh = ranks.max(time.perf_counter() - t0h)
-        host_leg = {"ms_per_step": elh / args.steps * 1e3,
-                    "ray_bounces_per_s": q_all * args.steps / elh,
+        host_leg = {"ms_per_step": elh / k_leg * 1e3,
+                    "ray_bounces_per_s": q_all * k_leg / elh,
                     "host_path_ms": float(ranks.max(np.median(host_conv))),
                     "host_bytes_per_gpu_per_step": 3 * 4 * frames,
                     "why": "the PCIe-inclusive rate, not the value: each step renders and then convolves the file "
@@ -825,7 +963,6 @@ def main(argv=None) -> int:
                            "slowest GPU"}
         g.set_frames_in_flight(args.frames_in_flight)
 
-    n_tris = int(stats["n_scene_tris"] + stats["n_receiver_tris"])
     moving = None
     if args.c5_frames > 0:  # C5 on a group of its own: 1M rays per frame in total, sharded over the GPUs
         s5 = RenderSettings(rays=C5["rays"], ir_length_in_seconds=2, sample_rate=C5["sample_rate"], base_power=3.62,
@@ -855,77 +992,16 @@ def main(argv=None) -> int:
     conv_traffic, conv_traffic_why = conv_profile_guard(load_profile(CONV_TRAFFIC), args.workload)
     parity, parity_why = profile_guard(load_profile(FULL_LAUNCH_PARITY), args.workload, st0,
                                        ("workload", "tree_hash", "trace_kernel_id"))
-    # unique stereo frames: the file once per step when it is time-block sharded (or on one GPU), every
-    # GPU's copy with --replicated-convolution
     conv_frames_s = unique_frames / (conv_ms_max * 1e-3)  # the convolution kernels' own window
-    conv_frames_step = unique_frames * args.steps / elapsed  # the pipeline: frames convolved per timed step
-    result = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "ray-bounces/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if wl.get("total") else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic: deterministic conference.obj stand-in (seed 42; conference.obj is missing from the "
-                "reference checkout) + the reference's own audio (" + wl["audio"] + ", channel 0)",
-        "config": {
-            "workload": wl["desc"],
-            "scene_triangles": n_tris,
-            "rays_per_gpu": total_rays // world,
-            "max_bounces": wl["max_bounces"],
-            "sample_rate": wl["sample_rate"],
-            "ir_len": ir_len,
-            "audio_frames": frames,
-            "convolution": ("one GPU: the whole file" if world == 1 else
-                            (f"time-block sharded over {world} GPUs (arx_group_convolute_device): rank r owns the "
-                             f"output frames of block pairs [r P/{world}, (r+1) P/{world}) and re-makes its seam pair, "
-                             "no collective" if conv_plan_shards else
-                             "this plan has no chained pass: every GPU convolves the whole file")
-                            if sharded_conv else f"replicas: each of the {world} GPUs convolves the whole file"),
-            "convolved_frames_per_step": unique_frames,
-            "conv_frames_owned_rank0": [int(own[0][0]), int(own[0][1])],
-            "frames_in_flight": args.frames_in_flight,
-            # the persistent trace grid (arx_stats.trace_grid_cus): half the CUs' wave slots per launch
-            # with frames in flight, so two frames' launches run side by side; the full device with one
-            "trace_grid_cus": {"timed_steps": int(st0["trace_grid_cus"]), "kernel_times_leg": grid_cus_single},
-            "parallelism": (f"ray-shard x{world}, "
-                            + ("REHEARSAL (--debug-oversubscribe): the ranks' histograms summed on device 0, no RCCL"
-                               if args.debug_oversubscribe else
-                               "native RCCL int64 IR all-reduce per step" if world > 1 else
-                               "one rank: the group's RCCL communicator exists but arx_group_render skips its no-op "
-                               "IR all-reduce (arx_group.cpp; tests/test_gpu_collectives.py forces it on one GPU)")
-                            + " (arx_group: "
-                            + ("one process, ncclCommInitAll over devices " + ",".join(map(str, plan["devices"]))
-                               if plan["mode"] == "local" and not args.debug_oversubscribe else
-                               "one process, device 0 listed " + str(world) + " times" if args.debug_oversubscribe
-                               else f"one process per GPU, ncclCommInitRank, rank {rank}")
-                            + ")"),
-        },
-        "runtime": runtime_info(),
-        "collectives_issued": dict(collectives, forced=bool(args.debug_force_collectives),
-                                   note="RCCL collectives the headline group issued up to the end of the timed steps "
-                                        "(a one-rank group skips them unless forced)"),
-        "setup_s_rank0": setup_s,
+    result["config"]["trace_grid_cus"]["kernel_times_leg"] = grid_cus_single
+    result.update({
         "single_frame": single_frame,
-        "kernel_times_leg": {"steps": args.steps, "warmup": args.warmup, "frames_in_flight": 1,
+        "kernel_times_leg": {"steps": k_leg, "warmup": args.warmup, "frames_in_flight": 1,
                              "ms_per_step": timed_leg_ms,
                              "why": "W + K more single-frame steps with the renderer's per-launch HIP events on "
                                     "(arx_set_timing): phases_ms_rank0 and the rooflines are this leg's launches; "
                                     "its step time against single_frame's is what the four event markers cost a "
                                     "step"},
-        "preroll": {"steps": pre_steps, "seconds_rank0": preroll_s,
-                    "why": "untimed steps before the W warmup steps, until the GPU runs at its sustained clock "
-                           "(a fresh or idle MI355X ramps over its first ~10 C3 launches, 2.95 -> 2.67 ms; "
-                           "profiles/r04/trace_ramp.json)"},
-        "ray_bounces_per_step": q_all,
-        "nominal_ray_bounces_per_s": total_rays * wl["max_bounces"] * args.steps / elapsed,
-        "receiver_hits_per_step_rank0": int(st0["receiver_hits"]),
-        "convolved_frames_per_s": conv_frames_step,
         "convolved_frames_per_s_kernel_window": conv_frames_s,
         "convolved_frames_per_s_labels": {
             "convolved_frames_per_s": "whole job, per timed step: unique stereo frames convolved "
@@ -1000,7 +1076,7 @@ def main(argv=None) -> int:
                               "FETCH_SIZE x2 + WRITE_SIZE per pass, the C3 convolution incl. IR spectra, one GPU): "
                               + conv_traffic_why,
         },
-    }
+    })
     if vmem and counts:
         # the trace's divergent 16-B gathers against the rate a microbenchmark of independent
         # divergent gathers reaches at this kernel's L1 / L2 / Infinity-Cache hit mix
@@ -1060,14 +1136,7 @@ def main(argv=None) -> int:
     wd.disarm()  # the CPU baseline below runs no GPU work
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(scene, receiver, wl, total_rays, audio_np, args.cpu_baseline_seconds)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    for b in bufs:
-        for x in b:
-            x.close()
-    ranks.barrier()
-    g.close()
-    return 0
+    return finish()
 
 
 if __name__ == "__main__":

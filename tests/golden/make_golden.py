@@ -101,6 +101,16 @@ def audio_fixtures() -> None:
                   os.path.join(HERE, "audio_clapper_48k_ch0.npz"))
 
 
+def reference_objs() -> list[str]:
+    """Relative paths of every *.obj in the reference checkout (hidden directories left out), sorted."""
+    out = []
+    for root, _, files in os.walk(REF):
+        if "/." in root:
+            continue
+        out += [os.path.relpath(os.path.join(root, f), REF) for f in files if f.endswith(".obj")]
+    return sorted(out)
+
+
 def main() -> int:
     if len(sys.argv) > 1 and sys.argv[1] == "audio":
         audio_fixtures()
@@ -151,6 +161,10 @@ def main() -> int:
                 names.append(line.split()[1])
     with open(os.path.join(HERE, "conference_materials.json"), "w") as fh:
         json.dump(names, fh)
+    # every *.obj of the reference checkout (names only): the cases of the differential OBJ sweep, so
+    # that the suite has the same tests whether or not the checkout is present
+    with open(os.path.join(HERE, "reference_objs.json"), "w") as fh:
+        json.dump(reference_objs(), fh, indent=1)
     print("fixtures written to", HERE)
     return 0
 

@@ -94,10 +94,65 @@ def test_more_gpus_than_visible_fails_loudly():
     assert "--gpus 64" in p.stderr
 
 
-def test_steps_beyond_the_timing_ring_are_refused():
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "100000"], capture_output=True,
-                       text=True, timeout=120)
-    assert p.returncode != 0 and "--steps" in p.stderr and p.stdout.strip() == ""
+def test_steps_may_pass_the_timing_ring_except_with_timing_events():
+    """--steps sets the number of timed steps, which record no per-launch events and so may pass the
+    renderer's timing ring; what reads the ring keeps within it: --timing-events refuses more steps,
+    and the --full legs that read per-launch times back run min(steps, ring) of them."""
+    from audiorenderingv2_amd._lib import lib
+
+    ring = int(lib().arx_timing_ring())
+    for args in (["--steps", "100000", "--timing-events"], ["--steps", "0"]):
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), *args], capture_output=True,
+                           text=True, timeout=120)
+        assert p.returncode != 0 and "--steps" in p.stderr and p.stdout.strip() == "", args
+    assert bench.leg_steps(100000, ring) == ring and bench.leg_steps(ring, ring) == ring
+    assert bench.leg_steps(20, ring) == 20
+
+
+class _FakeBuffer:
+    def __init__(self, a):
+        self.a = a
+
+    def to_numpy(self, dtype, count):
+        return self.a[:count].astype(dtype)
+
+
+class _FakeIrGroup:
+    def __init__(self, n_ranks, ir):
+        self.n_ranks, self.ir = n_ranks, ir
+
+    def get_ir(self):
+        return self.ir
+
+
+def test_dump_outputs_puts_the_shards_together(tmp_path):
+    """bench.dump_outputs: one process writes the IR and the whole convolved file, each member's
+    owned frames taken from its buffers (what lies outside a member's shard is never read into the
+    file); a rank of a multi-process job writes its own frames under its rank's name."""
+    import numpy as np
+
+    frames, own = 10, [(0, 4), (4, 10)]
+    ir = (np.arange(6, dtype=np.float32), -np.arange(6, dtype=np.float32))
+    want_l, want_r = np.arange(frames, dtype=np.float32) + 1, np.arange(frames, dtype=np.float32) + 101
+    bufs = []
+    for lo, hi in own:  # a member's buffers hold its shard and junk elsewhere
+        left, right = np.full(frames, 7e7, np.float32), np.full(frames, -7e7, np.float32)
+        left[lo:hi], right[lo:hi] = want_l[lo:hi], want_r[lo:hi]
+        bufs.append((None, _FakeBuffer(left), _FakeBuffer(right)))
+    one = tmp_path / "one_process"
+    bench.dump_outputs(str(one), _FakeIrGroup(2, ir), bufs, own, frames, 0, whole_file=False)
+    assert sorted(os.listdir(one)) == ["conv_left.npy", "conv_right.npy", "ir_left.npy", "ir_right.npy"]
+    for name, want in (("ir_left", ir[0]), ("ir_right", ir[1]), ("conv_left", want_l), ("conv_right", want_r)):
+        got = np.load(one / (name + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, want), name
+    rank1 = tmp_path / "rank1"
+    bench.dump_outputs(str(rank1), _FakeIrGroup(2, ir), bufs[1:], own[1:], frames, 1, whole_file=False)
+    assert sorted(os.listdir(rank1)) == ["conv_left_rank1.npy", "conv_right_rank1.npy"]  # the IR is rank 0's to write
+    assert np.array_equal(np.load(rank1 / "conv_left_rank1.npy"), want_l[4:10])
+    whole = tmp_path / "replicas"
+    full = (None, _FakeBuffer(want_l), _FakeBuffer(want_r))
+    bench.dump_outputs(str(whole), _FakeIrGroup(2, ir), [full, full], own, frames, 0, whole_file=True)
+    assert np.array_equal(np.load(whole / "conv_right.npy"), want_r)
 
 
 class _FakeGroup:

@@ -167,20 +167,21 @@ def compare_obj_with_refdump(path):
         ref["header"]["shapes"], ref["header"]["materials"], ref["header"]["vertices"])
 
 
-def all_reference_objs():
-    if not os.path.isdir(REF):
-        return []
-    out = []
-    for root, _, files in os.walk(REF):
-        if "/." in root:
-            continue
-        out += [os.path.join(root, f) for f in files if f.endswith(".obj")]
-    return sorted(out)
+# The sweep's cases are the stored names of the checkout's *.obj files (tests/golden/reference_objs.json,
+# written by make_golden.py), so the suite holds the same tests with and without the checkout.
+with open(os.path.join(GOLDEN, "reference_objs.json")) as _fh:
+    REFERENCE_OBJS = json.load(_fh)
+
+
+@need_ref
+def test_stored_obj_names_are_every_obj_of_the_reference():
+    assert make_golden.reference_objs() == REFERENCE_OBJS
 
 
 @need_refdump
-@pytest.mark.parametrize("path", all_reference_objs(), ids=lambda p: os.path.relpath(p, REF))
-def test_every_reference_obj_matches_tinyobj(path):
+@pytest.mark.parametrize("rel", REFERENCE_OBJS)
+def test_every_reference_obj_matches_tinyobj(rel):
+    path = os.path.join(REF, rel)
     if os.path.getsize(path) > 20_000_000:
         pytest.skip("large model")
     compare_obj_with_refdump(path)

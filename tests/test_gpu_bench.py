@@ -1,7 +1,8 @@
 """bench.py's output contract on the GPU: exactly one JSON line on stdout with the keys the driver
-and the judge read (metric / value / unit / n_gpus / steps / warmup / ms_per_step / roofline /
-cpu_baseline ...), the work accounting consistent with the workload, and nothing else on stdout
-(RCCL's version banner goes to stderr)."""
+and the judge read (metric / value / unit / n_gpus / steps / warmup / ms_per_step, and with --full
+roofline / cpu_baseline ...), the work accounting consistent with the workload, and nothing else on
+stdout (RCCL's version banner goes to stderr).  A plain run times its steps only and, with
+--dump-outputs, writes the last step's IR and convolved file; the other legs run with --full."""
 import json
 import os
 import subprocess
@@ -15,8 +16,8 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_prints_one_contract_line():
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", "c2", "--steps", "2", "--warmup", "1",
-           "--c5-frames", "3", "--cpu-baseline-seconds", "1"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--workload", "c2", "--steps", "2",
+           "--warmup", "1", "--c5-frames", "3", "--cpu-baseline-seconds", "1"]
     p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -108,7 +109,7 @@ def test_bench_rank_path_under_torchrun():
     max-over-ranks timing) rehearsed at one rank."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29631", os.path.join(REPO, "bench.py"), "--gpus", "1", "--process-group",
-           "--workload", "c2", "--steps", "2", "--warmup", "1", "--c5-frames", "3", "--no-cpu-baseline"]
+           "--full", "--workload", "c2", "--steps", "2", "--warmup", "1", "--c5-frames", "3", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]
@@ -134,8 +135,8 @@ def test_bench_watchdog_ends_a_hung_step_with_one_line():
 def test_bench_forced_collectives_time_the_allreduce():
     """With the collectives forced at one rank, the line carries the measured all-reduce phase and
     the C5 leg's measured all-reduce percentiles."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", "c2", "--steps", "3", "--warmup", "1",
-           "--c5-frames", "5", "--no-cpu-baseline", "--no-streaming", "--no-reuse", "--no-host-leg",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--workload", "c2", "--steps", "3",
+           "--warmup", "1", "--c5-frames", "5", "--no-cpu-baseline", "--no-streaming", "--no-reuse", "--no-host-leg",
            "--debug-force-collectives"]
     p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -151,8 +152,8 @@ def test_bench_n_rank_bookkeeping_rehearsed_on_one_gpu():
     ray shards summed on the device, the file convolution time-block sharded over the 3 members).
     The line counts the 3-rank launch's ray-bounces, each convolved frame once, one frame in flight
     at N > 1, and says it is a rehearsal."""
-    base = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", "c2", "--steps", "3", "--warmup", "1",
-            "--c5-frames", "3", "--no-cpu-baseline", "--no-streaming", "--no-reuse", "--no-host-leg"]
+    base = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--workload", "c2", "--steps", "3",
+            "--warmup", "1", "--c5-frames", "3", "--no-cpu-baseline", "--no-streaming", "--no-reuse", "--no-host-leg"]
     p = subprocess.run(base + ["--gpus", "3", "--debug-oversubscribe"], cwd=REPO, capture_output=True, text=True,
                        timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -167,3 +168,82 @@ def test_bench_n_rank_bookkeeping_rehearsed_on_one_gpu():
     assert d["roofline_convolution"]["frames_rank0"] == e - b
     assert d["phases_ms_rank0"]["allreduce"] is None  # summed on the device: no RCCL collective
     assert d["moving_listener"]["gpus"] == 3 and d["moving_listener"]["rays_per_gpu"] == 1_000_000 // 3
+
+
+# ------------------------------------------------------------------ the plain run and its outputs --
+FULL_ONLY = ("single_frame", "kernel_times_leg", "phases_ms_rank0", "roofline", "roofline_convolution", "roofline_td",
+             "convolution_input_reuse", "host_buffers", "moving_listener", "moving_listener_rank_of_8", "streaming",
+             "cpu_baseline", "convolved_frames_per_s_kernel_window")
+DUMPED = ("ir_left", "ir_right", "conv_left", "conv_right")
+
+
+def _plain(out_dir, steps):
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", str(steps),
+           "--warmup", "1", "--dump-outputs", str(out_dir)]
+    p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[:2000]
+    return json.loads(lines[0])
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory):
+    out = tmp_path_factory.mktemp("bench_outputs")
+    return _plain(out, 3), out
+
+
+def test_plain_run_times_the_steps_and_nothing_else(plain_run):
+    """Without --full the line holds the headline fields and none of the other legs' (they never ran)."""
+    d, _ = plain_run
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "ray_bounces_per_step", "convolved_frames_per_s"):
+        assert k in d, k
+    assert not d["full"] and not [k for k in FULL_ONLY if k in d]
+    assert d["unit"] == "ray-bounces/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    # value = ray-bounces per step over the step time
+    assert abs(d["value"] - d["ray_bounces_per_step"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    rays = d["config"]["rays_per_gpu"]
+    assert rays <= d["ray_bounces_per_step"] <= rays * d["config"]["max_bounces"]
+    assert d["config"]["frames_in_flight"] == 3 and d["config"]["trace_grid_cus"]["timed_steps"] >= 2
+
+
+def test_dumped_outputs_are_the_last_steps_ir_and_convolution(plain_run):
+    """--dump-outputs: the stereo IR and the convolved file of the last timed step as float32 arrays,
+    and the convolution is that IR's (the f64 oracle block convolution of the same audio, to 1 ulp of
+    the largest sample, the bound of tests/test_gpu_parity.py's convolution checks)."""
+    import numpy as np
+
+    import pyoracle as po
+    from audiorenderingv2_amd.scene import reference_audio
+
+    d, out = plain_run
+    a = {n: np.load(os.path.join(out, n + ".npy")) for n in DUMPED}
+    assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in DUMPED)
+    ir_len, frames = d["config"]["ir_len"], d["config"]["audio_frames"]
+    for n in DUMPED:
+        assert a[n].dtype == np.float32 and a[n].shape == ((ir_len,) if n.startswith("ir") else (frames,)), n
+        assert np.isfinite(a[n]).all() and a[n].any(), n
+    x, sr = reference_audio("experimento")
+    for ir, got in ((a["ir_left"], a["conv_left"]), (a["ir_right"], a["conv_right"])):
+        ref = po.convolute_audio(x, sr, ir)
+        assert np.abs(got - ref).max() <= np.spacing(np.float32(np.abs(ref).max()))
+
+
+def test_dumped_outputs_repeat_and_steps_may_pass_the_timing_ring(plain_run, tmp_path):
+    """The same arguments give the same inputs, so a second process dumps the same bits, whatever
+    the number of timed steps -- here more than the renderer's per-launch timing ring holds, which a
+    plain run (no timing events) does not need."""
+    import numpy as np
+
+    from audiorenderingv2_amd._lib import lib
+
+    _, out = plain_run
+    steps = int(lib().arx_timing_ring()) + 44
+    d = _plain(tmp_path, steps)
+    assert d["steps"] == steps and d["ms_per_step"] > 0
+    for n in DUMPED:
+        one, two = np.load(os.path.join(out, n + ".npy")), np.load(os.path.join(tmp_path, n + ".npy"))
+        assert np.array_equal(one.view(np.uint32), two.view(np.uint32)), n

@@ -81,7 +81,7 @@ def _bench(args, torchrun_ranks=0, timeout=600):
             port = sk.getsockname()[1]
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={torchrun_ranks}",
                 "--master-addr=127.0.0.1", f"--master-port={port}"]
-    cmd += [os.path.join(REPO, "bench.py"), *args, "--workload", "c4", "--steps", "2", "--warmup", "1",
+    cmd += [os.path.join(REPO, "bench.py"), *args, "--full", "--workload", "c4", "--steps", "2", "--warmup", "1",
             "--c5-frames", "0", "--no-cpu-baseline", "--no-streaming", "--no-pipelined"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=REPO)
     assert res.returncode == 0, res.stderr[-4000:]

@@ -3,7 +3,7 @@
 # bench line.  TAG names the logs; K= restricts pytest (-k expression); NOBENCH=1 skips the bench,
 # NOSUITE=1 the rest of the suite.
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"
+cd "${ARX_REPO:-$(dirname "$0")/..}"
 RD=${RD:-r06}
 O=gpurun_out/$RD
 TAG=${TAG:-x}
@@ -26,7 +26,7 @@ if [ -z "${NOSUITE:-}" ]; then
     suite pytest_gpu_$TAG tests $ign || exit $?
 fi
 [ -n "${NOBENCH:-}" ] && exit 0
-timeout -k 10 300 python -u bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+timeout -k 10 300 python -u bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err
 rc=$?
 tail -c 3000 $O/bench_$TAG.json
 exit $rc

@@ -1,5 +1,5 @@
-"""The timed steps' trace launches in a rocprofv3 kernel trace of the default bench command (frames in
-flight): how many run side by side, their durations and the period between launch starts.
+"""The timed steps' trace launches in a rocprofv3 kernel trace of `bench.py --full` (frames in flight):
+how many run side by side, their durations and the period between launch starts.
 
 With frames in flight a ray-pool launch is sized for half the CUs' wave slots (arx_stats.trace_grid_cus),
 so two frames' launches should run concurrently for most of their length; this reads it off the trace.
@@ -12,6 +12,8 @@ import sys
 
 def main(trace_csv, bench_json):
     d = json.loads(open(bench_json).read().strip().splitlines()[-1])
+    if "phases_ms_rank0" not in d:  # the single-frame and kernel-times legs run only with --full
+        sys.exit("grid_overlap.py: the line and the trace must be of `bench.py --full`")
     rows = [r for r in csv.DictReader(open(trace_csv)) if r["Kernel_Name"].startswith("void arx::(anonymous namespace)::trace_kernel<128")]
     iv = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Grid_Size", r.get("Grid_Size_X", ""))) for r in rows)
     # the bench's first C3 segment: pre-roll, warmup, timed steps (frames in flight), then the

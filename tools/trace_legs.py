@@ -1,4 +1,4 @@
-"""Per-leg trace-kernel durations from a rocprofv3 kernel trace of the default bench command.
+"""Per-leg trace-kernel durations from a rocprofv3 kernel trace of `bench.py --full`.
 
 The bench's timed loop runs frames in flight, whose trace launches start while the previous frame's
 is still draining, so a launch's own duration there is not its time on the GPU; the per-launch time
@@ -14,6 +14,8 @@ import sys
 
 def main(trace_csv, bench_json):
     d = json.load(open(bench_json))
+    if "phases_ms_rank0" not in d:  # the single-frame and kernel-times legs run only with --full
+        sys.exit("trace_legs.py: the line and the trace must be of `bench.py --full`")
     wk = d["steps"] + d["warmup"]
     rows = [r for r in csv.DictReader(open(trace_csv)) if r["Kernel_Name"].startswith("void arx::(anonymous namespace)::trace_kernel<128")]
     iv = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Stream_Id"]) for r in rows)
