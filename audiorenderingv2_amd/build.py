@@ -25,9 +25,12 @@ OBJDIR = os.path.join(PKG, "_obj")
 LIB = os.path.join(PKG, "libarx.so")
 ARCH = os.environ.get("ARX_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["arx_trace.hip", "arx_receiver.hip", "arx_conv.hip", "arx_capi.cpp", "arx_group.cpp", "arx_bvh.cpp", "arx_io.cpp",
-           "arx_wide.cpp"]
-HEADERS = ["arx_layout.hpp", "arx_kernels.hpp", "arx_bvh.hpp", "arx_internal.hpp", "arx_wide.hpp", "arx_scene_share.hpp"]
+SOURCES = ["arx_trace.hip", "arx_receiver.hip", "arx_conv.hip", "arx_conv_stream.hip", "arx_capi.cpp", "arx_group.cpp",
+           "arx_bvh.cpp", "arx_io.cpp", "arx_wide.cpp"]
+# the file / live convolution's kernels and the FFT device code under them: the files conv_source_id hashes
+CONV_KERNEL_FILES = ("arx_conv_fft.hpp", "arx_conv_kernels.hpp")
+HEADERS = ["arx_layout.hpp", "arx_kernels.hpp", "arx_bvh.hpp", "arx_internal.hpp", "arx_wide.hpp", "arx_scene_share.hpp",
+           *CONV_KERNEL_FILES]
 
 COMMON = [
     "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -79,9 +82,10 @@ def trace_source_id(defines: tuple[str, ...] = ()) -> str:
 
 
 def conv_source_id(defines: tuple[str, ...] = ()) -> str:
-    """The same identity for the file convolution's kernels (arx_conv.hip; arx_conv_kernel_id): the
-    guard of the stored convolution traffic profile."""
-    return _source_id(("arx_conv.hip",), defines)
+    """The same identity for the file convolution's kernels (CONV_KERNEL_FILES; compiled into
+    arx_conv.hip as arx_conv_kernel_id): the guard of the stored convolution traffic profile."""
+    # arx_conv.hip (plans, scratch, launchers) is not part of it: a host edit does not change the kernels
+    return _source_id(CONV_KERNEL_FILES, defines)
 
 
 SOURCE_IDS = {"arx_trace.hip": ("ARX_TRACE_SRC_ID", trace_source_id), "arx_conv.hip": ("ARX_CONV_SRC_ID", conv_source_id)}

@@ -1761,7 +1761,7 @@ arx_status arx_debug_ray_directions(uint64_t seed, uint64_t first, uint64_t coun
     return ARX_OK;
 }
 
-// ---- streaming convolution (UPOLS, arx_conv.hip) --------------------------------------------------
+// ---- streaming convolution (UPOLS, arx_conv_stream.hip) -------------------------------------------
 }  // extern "C"
 
 extern "C" {

@@ -77,7 +77,7 @@ hipError_t launch_requant16(const BvhNode* coded, uint64_t n, const QGrid& g, QN
 hipError_t launch_requant_w4(const W4NodeF* nodes, uint64_t n, const QGrid& g, uint4* wbuf, unsigned int* flag,
                              unsigned int flag_value, hipStream_t s);
 
-// ---- convolution (arx_conv.hip) ----
+// ---- convolution (arx_conv.hip; its kernels: arx_conv_kernels.hpp, arx_conv_fft.hpp) ----
 struct ConvPlan;  // opaque, defined in arx_conv.hip
 ConvPlan* conv_plan_create(int32_t ir_len, int32_t sample_rate, int device, char* err, size_t errlen);
 void conv_plan_destroy(ConvPlan* p);
@@ -110,10 +110,12 @@ int64_t conv_prepared_frames(const ConvPlan* p);
 // L/R into 2*ir_len doubles (AudioRenderer.cpp:593-651, kernels.cu:345-377, 450-487).
 hipError_t conv_run_live(ConvPlan* p, const double* d_in, int64_t n_in, double* d_out_interleaved, hipStream_t s);
 int32_t conv_plan_block(const ConvPlan* p);
-// identity of the convolution kernels in this build (build.py conv_source_id; arx_conv_kernel_id)
+// identity of the convolution kernels in this build (arx_conv_kernel_id): build.py conv_source_id's
+// hash of the kernel headers, which the stored traffic profile that bench.py reads must match --
+// host-only edits of arx_conv.hip leave it, and the profile, valid
 uint64_t conv_kernel_source_id();
 
-// ---- streaming convolution (arx_conv.hip): uniformly partitioned overlap-save, f64 ----
+// ---- streaming convolution (arx_conv_stream.hip): uniformly partitioned overlap-save, f64 ----
 struct StreamPlan;  // opaque
 // block: frames per callback (<= 4096); FFT size = the power of two >= 2*block.
 StreamPlan* stream_plan_create(int32_t ir_len, int32_t block, int device, char* err, size_t errlen);

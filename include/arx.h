@@ -206,8 +206,9 @@ arx_status arx_set_timing(arx_renderer* r, int32_t on);
  * count, and bench.py uses a stored profile only when all three match its own run.  No
  * reference counterpart (measurement plumbing). */
 uint64_t arx_trace_kernel_id(void);
-/* The same for the file convolution's kernels (build.py conv_source_id): the guard of the stored
- * convolution traffic profile (profiles/<round>/conv_traffic.json). */
+/* The same for the file convolution's kernels (build.py conv_source_id: the kernel headers
+ * arx_conv_fft.hpp and arx_conv_kernels.hpp, not the host code that launches them): the guard of
+ * the stored convolution traffic profile (profiles/<round>/conv_traffic.json). */
 uint64_t arx_conv_kernel_id(void);
 /* Replace the renderer's IR with caller data (host, ir_len floats per ear), e.g. a stored or
  * measured IR; the next convolution uses it.  No reference equivalent (its IR only comes

@@ -44,6 +44,19 @@ def test_trace_kernel_id_is_the_build_source_hash():
     assert build.trace_source_id(("ARX_TRACE_LEAFFLAT=1",)) != build.trace_source_id()
 
 
+def test_conv_kernel_id_is_the_hash_of_the_kernel_files():
+    """The same for the convolution: the library reports build.py's hash of the kernel headers (the
+    guard of the stored traffic profile).  The host file that launches them is not part of it, so a
+    host-only edit keeps the profile; an experiment macro gives another identity."""
+    from audiorenderingv2_amd import build
+    kid = int(_lib.lib().arx_conv_kernel_id())
+    assert kid != 0
+    assert kid == int(build.conv_source_id()[:-3], 16)
+    assert "arx_conv.hip" not in build.CONV_KERNEL_FILES
+    assert all(os.path.exists(os.path.join(build.CSRC, f)) for f in build.CONV_KERNEL_FILES)
+    assert build.conv_source_id(("ARX_CONV_TCA=4",)) != build.conv_source_id()
+
+
 def test_status_strings_and_errors():
     L = _lib.lib()
     assert L.arx_status_string(0) == b"ok"
