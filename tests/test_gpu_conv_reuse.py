@@ -37,7 +37,8 @@ def fetch(r, a, b, n):
     (48000, 2, 807498, "direct"),      # C3: A_Clapper_Board's length, 300 x 320, chained pass C
     (16000, 2, 128000 + 77, "direct"),  # C2: experimento's length (+ a ragged tail)
     (16000, 1, 70000, "copy"),          # ir_len = sr: no chained pass C, the kept copy
-    (1100, 2, 6000, "copy"),            # power-of-two plan
+    (1100, 2, 6000, "copy"),            # power-of-two plan, 64 x 64 (generic radix-4 FFTs)
+    (17000, 2, 60000, "copy"),          # power-of-two plan, 256 x 256 (the one-wave FFTs)
 ])
 def test_prepared_equals_device_convolution(sr, secs, length, plan):
     rng = np.random.default_rng(sr + length)

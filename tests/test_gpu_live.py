@@ -52,9 +52,12 @@ def test_prepared_spectra_follow_new_ir():
 
 @pytest.mark.parametrize("sr,secs", [(16000, 2), (22050, 1), (32000, 2)])
 def test_live_block_256_point_plans(sr, secs):
-    """Plans whose sub-FFTs are 256 points (M = 2^16: 16 kHz x 2 s, 22.05 kHz x 1 s) or mix
-    256-point columns with 512-point rows (M = 2^17: 32 kHz x 2 s) -- the radix-4 wave FFTs."""
+    """Direct mixed-radix live plans of the usual rates (160 x 200 at 16 kHz x 2 s, 147 x 150 at
+    22.05 kHz x 1 s, 250 x 256 at 32 kHz x 2 s).  These shapes were power-of-two plans with 256- and
+    512-point sub-FFTs before the direct path took them (the test's name dates from then); the
+    power-of-two live plans are test_gpu_conv_pow2.py's."""
     r, (irl, irr) = live_renderer(sr=sr, secs=secs, seed=sr)
+    assert r.conv_plan(live=True).startswith("mixed-radix direct circular")
     x = np.random.default_rng(sr).uniform(-1, 1, min(4096, sr))
     assert rel_err(r.convoluteLiveInput(x), po.convolute_live_block(x, irl, irr)) < 1e-12
 
