@@ -155,6 +155,10 @@ SIGNATURES = {
     "arx_stream_info": (C.c_int, [_P, _I32, _I32, _I32]),
     "arx_stream_process": (C.c_int, [_P, _D, C.c_size_t, _D, C.c_size_t]),
     "arx_stream_process_device": (C.c_int, [_P, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "arx_stream_fade_weights": (C.c_int, [C.c_int32, C.c_int32, _D]),
+    "arx_stream_set_crossfade": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "arx_stream_get_crossfade": (C.c_int, [_P, _I32, _I32]),
+    "arx_stream_crossfades": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "arx_group_create": (C.c_int, [C.POINTER(ArxConfig), _I32, C.c_int32, C.POINTER(_P)]),
     "arx_group_unique_id": (C.c_int, [C.c_char_p, C.c_size_t]),
     "arx_group_create_rank": (C.c_int, [C.POINTER(ArxConfig), C.c_int32, C.c_int32, C.c_char_p, C.c_size_t,

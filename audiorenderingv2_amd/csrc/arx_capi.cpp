@@ -532,6 +532,8 @@ struct arx_stream {
     int device = 0;
     StreamPlan* plan = nullptr;
     uint64_t ir_generation = ~0ull;  // the IR the partition spectra were made from
+    int32_t fade_shape = ARX_FADE_HANN;  // arx_stream_set_crossfade (the frames: stream_plan_fade)
+    uint64_t crossfades = 0;             // transition blocks processed
     double* d_in = nullptr;          // host-API staging: block frames in, 2 * block out
     double* d_out = nullptr;
 };
@@ -1829,16 +1831,73 @@ arx_status arx_stream_process_device(arx_stream* s, const double* d_in, size_t n
     arx_renderer* r = s->r;
     ARX_HIP(hipSetDevice(r->cfg.device));
     if (const arx_status w = fif_wait_conv(r); w != ARX_OK) return w;  // the stream's delay line and spectra
+    bool transition = false;
     if (s->ir_generation != r->ir_generation) {  // the IR changed: new partition spectra
-        ARX_HIP(stream_set_ir(s->plan, r->d_ir, r->d_ir + r->ir_len, r->stream));
+        // a transition block: a fade is on and the last block (since creation or the last reset) ran
+        // with the spectra that are current until now; they become the previous set
+        transition = stream_plan_fade(s->plan) > 0 && s->ir_generation != ~0ull && stream_plan_blocks(s->plan) > 0;
+        ARX_HIP(stream_set_ir(s->plan, r->d_ir, r->d_ir + r->ir_len, transition, r->stream));
         s->ir_generation = r->ir_generation;
     }
     const int slot = (int)(r->live_launches % arx_renderer::kTraceRing);
     ARX_HIP(hipEventRecord(r->lev0[slot], r->stream));
-    ARX_HIP(stream_run(s->plan, d_in, (int64_t)n_frames, d_out, r->stream));
+    if (transition) {
+        ARX_HIP(stream_run_xfade(s->plan, d_in, (int64_t)n_frames, d_out, r->stream));
+        ++s->crossfades;
+    } else {
+        ARX_HIP(stream_run(s->plan, d_in, (int64_t)n_frames, d_out, r->stream));
+    }
     ARX_HIP(hipEventRecord(r->lev1[slot], r->stream));
     ++r->live_launches;
     return fif_done_conv(r);
+}
+
+arx_status arx_stream_fade_weights(int32_t shape, int32_t fade_frames, double* w) {
+    if (fade_frames <= 0) return fail(ARX_ERR_INVALID_ARGUMENT, "fade of %d frames: must be positive", fade_frames);
+    if (shape != ARX_FADE_LINEAR && shape != ARX_FADE_HANN) return fail(ARX_ERR_INVALID_ARGUMENT, "unknown fade shape %d", shape);
+    if (!w) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL buffer");
+    const double pi = 3.14159265358979323846;
+    for (int32_t i = 0; i < fade_frames; ++i) {
+        const double t = ((double)i + 0.5) / (double)fade_frames;
+        w[i] = shape == ARX_FADE_LINEAR ? t : 0.5 - 0.5 * std::cos(pi * t);
+    }
+    return ARX_OK;
+}
+
+arx_status arx_stream_set_crossfade(arx_stream* s, int32_t fade_frames, int32_t shape) {
+    if (const arx_status st0 = live_stream(s); st0 != ARX_OK) return st0;
+    const int32_t B = stream_plan_block(s->plan);
+    if (fade_frames < 0 || fade_frames > B)
+        return fail(ARX_ERR_INVALID_ARGUMENT, "fade of %d frames: must be in [0, block = %d]", fade_frames, B);
+    if (shape != ARX_FADE_LINEAR && shape != ARX_FADE_HANN) return fail(ARX_ERR_INVALID_ARGUMENT, "unknown fade shape %d", shape);
+    std::vector<double> w((size_t)fade_frames);
+    if (fade_frames > 0)
+        if (const arx_status st = arx_stream_fade_weights(shape, fade_frames, w.data()); st != ARX_OK) return st;
+    arx_renderer* r = s->r;
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    if (const arx_status wt = fif_wait_conv(r); wt != ARX_OK) return wt;  // blocks in flight read the weights
+    const hipError_t e = stream_set_fade(s->plan, fade_frames, w.data(), r->stream);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return fail(ARX_ERR_OUT_OF_MEMORY, "the crossfade's second set of partition spectra");
+    }
+    ARX_HIP(e);
+    s->fade_shape = shape;
+    return fif_done_conv(r);
+}
+
+arx_status arx_stream_get_crossfade(const arx_stream* s, int32_t* fade_frames, int32_t* shape) {
+    if (const arx_status st0 = live_stream(s); st0 != ARX_OK) return st0;
+    if (fade_frames) *fade_frames = stream_plan_fade(s->plan);
+    if (shape) *shape = s->fade_shape;
+    return ARX_OK;
+}
+
+arx_status arx_stream_crossfades(const arx_stream* s, uint64_t* n) {
+    if (const arx_status st0 = live_stream(s); st0 != ARX_OK) return st0;
+    if (!n) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *n = s->crossfades;
+    return ARX_OK;
 }
 
 arx_status arx_stream_process(arx_stream* s, const double* h_in, size_t n_frames, double* h_out, size_t out_len) {

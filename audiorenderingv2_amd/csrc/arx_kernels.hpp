@@ -121,10 +121,22 @@ struct StreamPlan;  // opaque
 StreamPlan* stream_plan_create(int32_t ir_len, int32_t block, int device, char* err, size_t errlen);
 void stream_plan_destroy(StreamPlan* p);
 hipError_t stream_reset(StreamPlan* p, hipStream_t s);                      // zero history + delay line
-hipError_t stream_set_ir(StreamPlan* p, const float* d_ir_left, const float* d_ir_right, hipStream_t s);
+// Partition spectra of a new IR into the current set.  keep_previous (needs stream_set_fade): the
+// set the last block used is kept as the previous one (a pointer swap) and the other is rebuilt.
+hipError_t stream_set_ir(StreamPlan* p, const float* d_ir_left, const float* d_ir_right, bool keep_previous,
+                         hipStream_t s);
 // One block (n_in <= block f64 frames, zero padded) -> 2*block zipped L/R doubles.
 hipError_t stream_run(StreamPlan* p, const double* d_in, int64_t n_in, double* d_out_interleaved, hipStream_t s);
+// Crossfade of fade_frames in [0, block] frames with the weights h_w[0..fade_frames) of the current
+// set (0: off, h_w unused).  The first fade allocates the previous set and the weight table
+// (hipErrorOutOfMemory); the table is uploaded on s.
+hipError_t stream_set_fade(StreamPlan* p, int32_t fade_frames, const double* h_w, hipStream_t s);
+// A transition block: stream_run with both sets, frame i < fade as fma(w[i], y_cur - y_prev, y_prev).
+hipError_t stream_run_xfade(StreamPlan* p, const double* d_in, int64_t n_in, double* d_out_interleaved,
+                            hipStream_t s);
 int32_t stream_plan_block(const StreamPlan* p);
+int64_t stream_plan_blocks(const StreamPlan* p);  // processed since the last reset
+int32_t stream_plan_fade(const StreamPlan* p);
 int32_t stream_plan_partitions(const StreamPlan* p);
 int32_t stream_plan_fft(const StreamPlan* p);
 

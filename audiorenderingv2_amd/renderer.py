@@ -335,15 +335,39 @@ class AudioRenderer:
         return int(n.value)
 
 
+FADE_SHAPES = ("linear", "hann")  # ARX_FADE_LINEAR, ARX_FADE_HANN
+
+
+def _fade_shape(fade: str | int) -> int:
+    """A shape's number; one that is neither a known name nor an int goes to the library as -1 (rejected)."""
+    if isinstance(fade, str):
+        return FADE_SHAPES.index(fade) if fade in FADE_SHAPES else -1
+    return int(fade)
+
+
+def fade_weights(shape: str | int, n: int) -> np.ndarray:
+    """arx_stream_fade_weights (host only): the new IR's weight on each of a transition block's first
+    n frames -- the table a LiveStream with that crossfade uses."""
+    w = np.empty(max(int(n), 0), np.float64)
+    check(lib().arx_stream_fade_weights(_fade_shape(shape), int(n), w.ctypes.data_as(C.POINTER(C.c_double))))
+    return w
+
+
 class LiveStream:
     """Streaming convolution of a renderer's IR (arx_stream_*, uniformly partitioned overlap-save
     in f64): process(block) consumes one block of <= block_frames f64 frames and returns
     block_frames output frames zipped L/R -- the linear convolution of the input stream with the
     current IR at the reference live path's scale (ir_len / (ir_len/2)).  The drop-in successor of
     convoluteLiveInput + CircularBuffer (AudioRenderer.cpp:593-661, main.cpp:99-135), whose
-    full-length circular result the reference's buffer wraps onto itself."""
+    full-length circular result the reference's buffer wraps onto itself.
 
-    def __init__(self, renderer: AudioRenderer, block_frames: int = 4096):
+    crossfade_frames > 0 (at most block_frames): the first block after an IR change is computed
+    with the old and the new IR and blended over its first crossfade_frames frames with
+    fade_weights(fade, crossfade_frames), instead of stepping to the new IR at the block boundary
+    (arx_stream_set_crossfade)."""
+
+    def __init__(self, renderer: AudioRenderer, block_frames: int = 4096, crossfade_frames: int = 0,
+                 fade: str | int = "hann"):
         self.renderer = renderer
         self._s = C.c_void_p()
         check(lib().arx_stream_create(renderer.handle, int(block_frames), C.byref(self._s)))
@@ -351,6 +375,26 @@ class LiveStream:
         b, p, n = C.c_int32(), C.c_int32(), C.c_int32()
         check(lib().arx_stream_info(self._s, C.byref(b), C.byref(p), C.byref(n)))
         self.block_frames, self.partitions, self.fft_size = b.value, p.value, n.value
+        if crossfade_frames:
+            self.set_crossfade(crossfade_frames, fade)
+
+    def set_crossfade(self, frames: int, fade: str | int = "hann") -> None:
+        """Crossfade over the first `frames` frames of a block whose IR is new; 0 = hard switch."""
+        check(lib().arx_stream_set_crossfade(self._s, int(frames), _fade_shape(fade)))
+
+    @property
+    def crossfade(self) -> tuple[int, str]:
+        """(frames, shape name) as set by set_crossfade; (0, "hann") on a fresh stream."""
+        f, sh = C.c_int32(), C.c_int32()
+        check(lib().arx_stream_get_crossfade(self._s, C.byref(f), C.byref(sh)))
+        return f.value, FADE_SHAPES[sh.value]
+
+    @property
+    def crossfades(self) -> int:
+        """Transition blocks processed since the stream was created."""
+        n = C.c_uint64()
+        check(lib().arx_stream_crossfades(self._s, C.byref(n)))
+        return int(n.value)
 
     def process(self, block: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(block, np.float64)

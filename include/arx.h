@@ -383,7 +383,9 @@ arx_status arx_conv_describe(arx_renderer* r, int which, char* buf, size_t len);
  * block_frames output frames zipped L/R (2*block_frames doubles) = the linear convolution of the
  * input stream with the renderer's current IR, scaled like the reference's live path
  * (ir_len / (ir_len/2), normalizeBuffers).  Latency: one block.  A new IR (render, set_ir) applies
- * from the next block on; the input history is kept.  block_frames in [1, min(4096, ir_len)]. */
+ * from the next block on; the input history is kept, so the stream does not restart -- but without
+ * a crossfade (below; off by default) the output steps from x * h_old to x * h_new within one
+ * sample at that block boundary.  block_frames in [1, min(4096, ir_len)]. */
 typedef struct arx_stream arx_stream;
 arx_status arx_stream_create(arx_renderer* r, int32_t block_frames, arx_stream** out);
 void arx_stream_destroy(arx_stream* s);
@@ -392,6 +394,39 @@ arx_status arx_stream_info(const arx_stream* s, int32_t* block_frames, int32_t* 
 arx_status arx_stream_process(arx_stream* s, const double* h_in, size_t n_frames, double* h_out, size_t out_len);
 /* Same on device buffers (n_frames f64 in, 2*block_frames f64 out), no host synchronisation. */
 arx_status arx_stream_process_device(arx_stream* s, const double* d_in, size_t n_frames, double* d_out);
+
+/* Crossfade at an IR change.  The stream keeps two sets of partition spectra: the current one and,
+ * once a fade was enabled, the one the previous block used (allocated by the first call that
+ * enables a fade, the size of the first: 3 MB at 48 kHz x 2 s x 4096 frames;
+ * ARX_ERR_OUT_OF_MEMORY if that fails).  A block is a transition block when fade_frames > 0, the
+ * renderer's IR generation differs from the one the current spectra were made from, and the stream
+ * has processed at least one block since it was created or last reset.  On a transition block the
+ * two sets are swapped, the new current set is built, both outputs are computed from the same
+ * delay line (this block's input included), and per ear
+ *     out[i] = fma(w[i], y_new[i] - y_old[i], y_old[i])  for frames i < fade_frames,
+ *     out[i] = y_new[i]                                  after,
+ * both y already scaled.  The first block of a stream and the first block after arx_stream_reset
+ * are never transition blocks: they use the current IR only.  Several IR changes between two
+ * blocks count as one (the old set is whatever the previous block used); an IR change before each
+ * of two consecutive blocks makes two consecutive transition blocks, each from the previous
+ * block's IR to its own.  With fade_frames == 0 the stream runs the kernels it always ran, to the
+ * same bits; with a fade enabled every block that is no transition does too, and so does a
+ * transition between two IRs with the same samples (arx_set_ir with the same data bumps the
+ * generation).  Nothing here adds a host or device synchronisation to arx_stream_process*: the
+ * weight table is uploaded by arx_stream_set_crossfade, ordered on the renderer's stream like
+ * arx_stream_reset, and holds exactly arx_stream_fade_weights' values.  Fades longer than a block
+ * and fades on the compat path (arx_convolute_live_block) are not provided. */
+#define ARX_FADE_LINEAR 0
+#define ARX_FADE_HANN   1
+/* Host only.  w[0..fade_frames) = the weight of the NEW IR's output on frame i of a transition block:
+ * t = (i + 0.5) / fade_frames;  LINEAR: w = t;  HANN: w = 0.5 - 0.5 cos(pi t).  Complementary
+ * (w[i] + w[F-1-i] == 1 to rounding), strictly inside (0, 1), increasing. */
+arx_status arx_stream_fade_weights(int32_t shape, int32_t fade_frames, double* w);
+/* fade_frames in [0, block_frames]; 0 (the default) = the hard switch. */
+arx_status arx_stream_set_crossfade(arx_stream* s, int32_t fade_frames, int32_t shape);
+arx_status arx_stream_get_crossfade(const arx_stream* s, int32_t* fade_frames, int32_t* shape);
+/* Transition blocks processed since the stream was created. */
+arx_status arx_stream_crossfades(const arx_stream* s, uint64_t* n);
 
 /* Tests only: issue every collective of the group even at one rank -- the histogram all-reduce of
  * arx_group_render (with frames in flight on every member's frame stream, chained by events), the

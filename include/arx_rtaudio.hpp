@@ -67,7 +67,9 @@ inline int audio_handler_with_mic(void* outputBuffer, void* inputBuffer, unsigne
 
 // The same duplex callback over the streaming convolution (arx_stream_*, d->stream created with
 // block_frames = the stream's nBufferFrames; any other buffer size aborts the stream): the output block is the linear convolution of the
-// mic stream with the IR, one block of latency, no circular wrap and no CircularBuffer.
+// mic stream with the IR, one block of latency, no circular wrap and no CircularBuffer.  Without a
+// crossfade a new IR steps in at a block boundary (a click on every listener move): the caller
+// enables the fade on d->stream once, arx_stream_set_crossfade(d->stream, nBufferFrames, ARX_FADE_HANN).
 inline int audio_handler_with_mic_stream(void* outputBuffer, void* inputBuffer, unsigned int nBufferFrames,
                                          double /*streamTime*/, unsigned int /*status*/, void* data) {
     MicCallbackData* d = static_cast<MicCallbackData*>(data);
