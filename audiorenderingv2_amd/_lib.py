@@ -48,6 +48,23 @@ class ArxStats(C.Structure):
     ]
 
 
+class ArxAcoustics(C.Structure):
+    """arx_acoustics: one channel's room-acoustic parameters (8-byte fields first, no padding)."""
+    _fields_ = [
+        ("total", C.c_int64), ("unit", C.c_double),
+        ("edt_s", C.c_double), ("t20_s", C.c_double), ("t30_s", C.c_double),
+        ("c50_db", C.c_double), ("c80_db", C.c_double), ("d50", C.c_double), ("ts_s", C.c_double),
+        ("onset_bin", C.c_int32), ("last_bin", C.c_int32),
+        ("edt_bins", C.c_int32 * 2), ("t20_bins", C.c_int32 * 2), ("t30_bins", C.c_int32 * 2),
+        ("valid", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+# include/arx.h ARX_ACOUSTICS_C* (the level tests' f64 literals) and ARX_VALID_* (bit order)
+ACOUSTICS_LEVELS = {5: 3.1622776601683794e-01, 10: 1.0000000000000001e-01, 25: 3.1622776601683794e-03,
+                    35: 3.1622776601683794e-04}
+ACOUSTICS_VALID = ("edt", "t20", "t30", "c50", "c80", "d50", "ts")
+
 PATH_MAX = 1024
 NAME_MAX = 128
 MAX_MATERIALS = 256
@@ -137,6 +154,16 @@ SIGNATURES = {
     "arx_trace_times": (C.c_int, [_P, _D, C.c_size_t, C.POINTER(C.c_size_t)]),
     "arx_conv_times": (C.c_int, [_P, _D, C.c_size_t, C.POINTER(C.c_size_t)]),
     "arx_live_times": (C.c_int, [_P, _D, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "arx_analyze_ir": (C.c_int, [_P]),
+    "arx_set_auto_analyze": (C.c_int, [_P, C.c_int32]),
+    "arx_get_acoustics": (C.c_int, [_P, C.c_int32, C.POINTER(ArxAcoustics)]),
+    "arx_edc_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "arx_copy_edc": (C.c_int, [_P, C.c_int32, _I64, C.c_size_t]),
+    "arx_analysis_times": (C.c_int, [_P, _D, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "arx_acoustics_from_histogram": (C.c_int, [_I64, _I64, C.c_size_t, C.c_int32, C.c_double,
+                                               C.POINTER(ArxAcoustics)]),
+    "arx_edc_from_histogram": (C.c_int, [_I64, C.c_size_t, _I64]),
+    "arx_debug_set_scan_shape": (C.c_int, [_P, C.c_int32]),
     "arx_timing_ring": (C.c_int32, []),
     "arx_trace_kernel_id": (C.c_uint64, []),
     "arx_conv_kernel_id": (C.c_uint64, []),

@@ -168,12 +168,16 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("arg", nargs="?")
     ap.add_argument("--receiver-dir")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--acoustics", action="store_true",
+                    help="write the first render's room-acoustic parameters (EDT, T20, T30, C50, C80, D50, Ts of the "
+                         "left, right and summed histogram) to output_acoustics.json, next to the IR dump")
     a = ap.parse_args(argv)
     try:
         if a.mode == "main":
             raise SystemExit("interactive mode (GLFW window + RtAudio devices) is not provided; "
                              "use `export` or `experiment`")
         ctx = Context.load(a.config, receiver_dir=a.receiver_dir, seed=a.seed)
+        ctx.renderer.set_write_acoustics_to_file_flag(a.acoustics)
         if a.mode == "export":
             export_audio(ctx, a.arg or "Result.wav")
         else:

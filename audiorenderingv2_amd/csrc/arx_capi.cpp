@@ -795,6 +795,11 @@ arx_status arx_live_times(arx_renderer* r, double* ms, size_t n, size_t* n_out) 
              : fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
 }
 
+arx_status arx_analysis_times(arx_renderer* r, double* ms, size_t n, size_t* n_out) {
+    return r ? ring_times(r, r->aev0, r->aev1, r->analysis_launches, ms, n, n_out)
+             : fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+}
+
 int32_t arx_timing_ring(void) { return arx_renderer::kTraceRing; }
 uint64_t arx_trace_kernel_id(void) { return trace_kernel_source_id(); }
 uint64_t arx_conv_kernel_id(void) { return conv_kernel_source_id(); }
@@ -908,6 +913,12 @@ float arx_material_absorption(const char* name, const char* const* names, const 
 }  // extern "C"
 
 namespace {
+void free_acoustics(arx_renderer::Acoustics& a) {
+    hipFree(a.d_edc);
+    hipFree(a.d_res);
+    hipFree(a.d_scratch);
+    a = arx_renderer::Acoustics{};
+}
 void free_frame_set(arx_renderer::FrameSet& f) {
     if (f.stream) hipStreamDestroy(f.stream);
     hipFree(f.d_hist);
@@ -915,6 +926,7 @@ void free_frame_set(arx_renderer::FrameSet& f) {
     hipFree(f.d_counters);
     hipFree(f.d_dirs);
     if (f.h_counters) hipHostFree(f.h_counters);
+    free_acoustics(f.acou);
     f = arx_renderer::FrameSet{};
 }
 }  // namespace
@@ -1033,6 +1045,7 @@ void arx_destroy(arx_renderer* r) {
     hipFree(r->d_hist);
     hipFree(r->d_ir);
     hipFree(r->d_counters);
+    free_acoustics(r->acou);
     hipFree(r->d_tree_flag);
     if (r->h_tree_flag) hipHostFree(r->h_tree_flag);
     hipFree(r->d_conv_in);
@@ -1045,6 +1058,8 @@ void arx_destroy(arx_renderer* r) {
         if (r->cev1[i]) hipEventDestroy(r->cev1[i]);
         if (r->lev0[i]) hipEventDestroy(r->lev0[i]);
         if (r->lev1[i]) hipEventDestroy(r->lev1[i]);
+        if (r->aev0[i]) hipEventDestroy(r->aev0[i]);
+        if (r->aev1[i]) hipEventDestroy(r->aev1[i]);
     }
     if (r->own_stream) hipStreamDestroy(r->own_stream);
     delete r;
@@ -1154,8 +1169,10 @@ arx_status arx_clear_histogram(arx_renderer* r) {
 arx_status arx::begin_frame(arx_renderer* r) {
     ARX_HIP(hipSetDevice(r->cfg.device));
     if (r->fif > 1) {  // a frame starts: it takes the next set's stream, histogram, IR, counters and directions
-        arx_renderer::FrameSet cur{r->own_stream, r->d_hist, r->d_ir, r->d_counters, r->h_counters, r->d_dirs, r->dirs_cap};
+        arx_renderer::FrameSet cur{r->own_stream, r->d_hist, r->d_ir, r->d_counters, r->h_counters, r->d_dirs, r->dirs_cap,
+                                   r->acou};
         const arx_renderer::FrameSet& nx = r->alt[0];
+        r->acou = nx.acou;
         r->own_stream = nx.stream;
         r->stream = r->own_stream;
         r->d_hist = nx.d_hist;
@@ -1168,6 +1185,7 @@ arx_status arx::begin_frame(arx_renderer* r) {
         r->alt[r->fif - 2] = cur;
         r->slot = (r->slot + 1) % r->fif;
     }
+    r->acou.queued = false;  // the new frame has no analysis yet
     return ARX_OK;
 }
 
@@ -1341,7 +1359,88 @@ arx_status arx_render(arx_renderer* r, double* render_ms) {
     if (st != ARX_OK) return st;
     st = arx_finalize_ir(r);
     if (st != ARX_OK) return st;
+    if (r->auto_analyze && (st = arx_analyze_ir(r)) != ARX_OK) return st;
     if (render_ms) return last_trace_ms(r, true, render_ms);
+    return ARX_OK;
+}
+
+arx_status arx_analyze_ir(arx_renderer* r) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    arx_renderer::Acoustics& a = r->acou;
+    if (!a.d_edc) {  // this frame set's first analysis
+        hipError_t e;
+        if ((e = hipMalloc(&a.d_edc, 3 * (size_t)r->ir_len * sizeof(long long))) != hipSuccess ||
+            (e = hipMalloc(&a.d_res, 3 * sizeof(arx_acoustics))) != hipSuccess ||
+            (e = hipMalloc(&a.d_scratch, acoustics_scratch_bytes())) != hipSuccess) {
+            free_acoustics(a);
+            return fail(e == hipErrorOutOfMemory ? ARX_ERR_OUT_OF_MEMORY : ARX_ERR_HIP, "arx_analyze_ir: %s",
+                        hipGetErrorString(e));
+        }
+    }
+    const bool timed = r->timing;
+    const int slot = (int)(r->analysis_launches % arx_renderer::kTraceRing);
+    if (timed) {
+        if (!r->aev0[slot]) ARX_HIP(hipEventCreateWithFlags(&r->aev0[slot], kTimingEvent));
+        if (!r->aev1[slot]) ARX_HIP(hipEventCreateWithFlags(&r->aev1[slot], kTimingEvent));
+        ARX_HIP(hipEventRecord(r->aev0[slot], r->stream));
+    }
+    AcousticsArgs args{};
+    args.hist = (const long long*)r->hist();
+    args.n = r->ir_len;
+    args.sample_rate = r->cfg.sample_rate;
+    args.unit = std::ldexp((double)initial_energy(r->cfg), -arx_frac_bits(n_rays(r->cfg)));
+    args.edc = a.d_edc;
+    args.out = a.d_res;
+    args.scratch = a.d_scratch;
+    args.shape = r->scan_shape == 0 ? kScanDefault : r->scan_shape;
+    ARX_HIP(launch_acoustics(args, r->stream));
+    if (timed) {
+        ARX_HIP(hipEventRecord(r->aev1[slot], r->stream));
+        ++r->analysis_launches;
+    }
+    a.queued = true;
+    return ARX_OK;
+}
+
+arx_status arx_set_auto_analyze(arx_renderer* r, int32_t on) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    r->auto_analyze = on != 0;
+    return ARX_OK;
+}
+
+arx_status arx_debug_set_scan_shape(arx_renderer* r, int32_t shape) {
+    if (!r || shape < 0 || shape > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "scan shape: 0, 1 or 2");
+    r->scan_shape = shape;
+    return ARX_OK;
+}
+
+arx_status arx_get_acoustics(arx_renderer* r, int32_t channel, arx_acoustics* out) {
+    if (!r || !out) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (channel < 0 || channel > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "channel %d: 0 left, 1 right, 2 sum", channel);
+    if (!r->acou.queued) return fail(ARX_ERR_NOT_READY, "no analysis was queued for the last frame (arx_analyze_ir)");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    ARX_HIP(hipMemcpyAsync(out, r->acou.d_res + channel, sizeof(arx_acoustics), hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    return ARX_OK;
+}
+
+arx_status arx_edc_device(arx_renderer* r, int64_t** d_edc, size_t* n) {
+    if (!r || !d_edc) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *d_edc = (int64_t*)r->acou.d_edc;
+    if (n) *n = 3 * (size_t)r->ir_len;
+    return ARX_OK;
+}
+
+arx_status arx_copy_edc(arx_renderer* r, int32_t channel, int64_t* h_edc, size_t ir_len) {
+    if (!r || !h_edc) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (channel < 0 || channel > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "channel %d: 0 left, 1 right, 2 sum", channel);
+    if (ir_len != (size_t)r->ir_len) return fail(ARX_ERR_INVALID_ARGUMENT, "ir_len %zu != %d", ir_len, r->ir_len);
+    if (!r->acou.queued) return fail(ARX_ERR_NOT_READY, "no analysis was queued for the last frame (arx_analyze_ir)");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    ARX_HIP(hipMemcpyAsync(h_edc, r->acou.d_edc + (size_t)channel * ir_len, ir_len * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipStreamSynchronize(r->stream));
     return ARX_OK;
 }
 

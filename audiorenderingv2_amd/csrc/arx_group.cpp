@@ -522,8 +522,9 @@ arx_status arx_group_render(arx_group* g, double* render_ms) {
     }
     // 3. every member finalises the full IR
     for (arx_renderer* r : g->members) {
-        const arx_status st = arx_finalize_ir(r);
+        arx_status st = arx_finalize_ir(r);
         if (st != ARX_OK) return st;
+        if (r->auto_analyze && (st = arx_analyze_ir(r)) != ARX_OK) return st;
     }
     if (render_ms) {  // the reference's window (AudioRenderer.cpp:495-518): the longest shard trace
         double worst = 0.0;

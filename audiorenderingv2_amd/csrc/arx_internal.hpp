@@ -130,6 +130,8 @@ struct arx_renderer {
     uint64_t conv_launches = 0;
     hipEvent_t lev0[kTraceRing] = {}, lev1[kTraceRing] = {};
     uint64_t live_launches = 0;
+    hipEvent_t aev0[kTraceRing] = {}, aev1[kTraceRing] = {};  // analyses (arx_analysis_times); made by the first one
+    uint64_t analysis_launches = 0;
 
     float emitter[3] = {0.f, 0.f, 0.f};
     float center[3] = {0.f, 0.f, 0.f};
@@ -220,6 +222,18 @@ struct arx_renderer {
     // group's all-reduce for the last all-reduce on the same communicator (ev_reduced).  `slot` names
     // the set in the fields above; last_* the set that did the last such step (-1: none yet).
     static constexpr int kMaxFrames = 3;
+    // A frame's room-acoustic analysis (arx_analyze_ir): decay curves (3*ir_len), results (3) and the
+    // kernels' scratch, allocated by the frame set's first analysis; queued: the frame that now owns
+    // the set was analysed (arx_get_acoustics).
+    struct Acoustics {
+        long long* d_edc = nullptr;
+        arx_acoustics* d_res = nullptr;
+        void* d_scratch = nullptr;
+        bool queued = false;
+    };
+    Acoustics acou;             // the current set's
+    bool auto_analyze = false;  // arx_set_auto_analyze
+    int32_t scan_shape = 0;     // arx_debug_set_scan_shape (0: the product's)
     struct FrameSet {
         hipStream_t stream = nullptr;
         unsigned long long* d_hist = nullptr;
@@ -228,6 +242,7 @@ struct arx_renderer {
         unsigned long long* h_counters = nullptr;
         void* d_dirs = nullptr;
         uint64_t dirs_cap = 0;
+        Acoustics acou;
     };
     int32_t fif = 1;
     int32_t slot = 0;

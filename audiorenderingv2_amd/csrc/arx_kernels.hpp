@@ -6,6 +6,8 @@
 
 #include "arx_layout.hpp"
 
+struct arx_acoustics;  // include/arx.h
+
 namespace arx {
 
 // Trace kernel (raygen + traversal + closest-hit + histogram, fused) over rays
@@ -31,6 +33,23 @@ hipError_t trace_kernel_occupancy(int fmt, bool small, int* vgprs, int* waves_ad
 bool trace_uses_small_block(const TraceArgs& a, int cus, bool force_global_stack);
 // identity of the trace kernel in this build (build.py trace_source_id; arx_trace_kernel_id)
 uint64_t trace_kernel_source_id();
+
+// ---- room-acoustic parameters (arx_acoustics.hip): decay curves and ISO 3382-1 statistics ----
+constexpr int kScanWorkgroup = 1, kScanTiled = 2;  // arx_debug_set_scan_shape
+constexpr int kScanDefault = kScanTiled;  // 7x faster at 96 000 bins
+struct AcousticsArgs {
+    const long long* hist;  // 2*n: [L | R]
+    int32_t n;              // ir_len
+    int32_t sample_rate;
+    double unit;            // e0 * 2^-frac_bits, copied into the results
+    long long* edc;         // out: 3*n, channels L, R, L + R
+    ::arx_acoustics* out;   // out: 3 results
+    void* scratch;          // acoustics_scratch_bytes()
+    int shape;              // kScanWorkgroup or kScanTiled
+};
+size_t acoustics_scratch_bytes();
+// Scan (one or two launches), fit partials, results: all on s, nothing waits on the host.
+hipError_t launch_acoustics(const AcousticsArgs& a, hipStream_t s);
 
 // ---- moving listener (arx_receiver.hip): transform + fixed-topology refit of the receiver ----
 struct RefitArgs {

@@ -10,6 +10,7 @@ from __future__ import annotations
 import atexit
 import ctypes as C
 import dataclasses
+import json
 import os
 import time
 import weakref
@@ -17,7 +18,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import ArxConfig, ArxStats, check, fptr, lib
+from ._lib import ACOUSTICS_VALID, ArxAcoustics, ArxConfig, ArxStats, check, fptr, lib
 from .formats import write_float_lines
 from .scene import Scene
 
@@ -181,11 +182,19 @@ class AudioRenderer:
             write_float_lines(os.path.join(self.output_dir, lp), L)
             write_float_lines(os.path.join(self.output_dir, rp), R)
             self.write_ir_to_file_flag = False
+        if self.write_acoustics_to_file_flag:  # next to the IR dump; no reference counterpart
+            self.analyze_ir()
+            name = "output_acoustics.json"
+            if self.experimentation:
+                name = os.path.join("experimentation", f"output_acoustics_{time.time_ns()}.json")
+            write_acoustics_json(os.path.join(self.output_dir, name), {ch: self.acoustics(ch) for ch in ACOUSTICS_CHANNELS})
+            self.write_acoustics_to_file_flag = False
         return ms.value
 
     # -- text dumps (AudioRenderer.cpp:525-567, 720-744; setters :780-788) -----------
     write_ir_to_file_flag = False
     write_output_to_file_flag = False
+    write_acoustics_to_file_flag = False
     experimentation = False
     output_dir = "."
 
@@ -194,6 +203,11 @@ class AudioRenderer:
 
     def set_write_output_to_file_flag(self, value: bool) -> None:
         self.write_output_to_file_flag = bool(value)
+
+    def set_write_acoustics_to_file_flag(self, value: bool) -> None:
+        """The next render() analyses its histogram and writes the three channels' room-acoustic
+        parameters to output_acoustics.json, next to the IR dump; then the flag clears."""
+        self.write_acoustics_to_file_flag = bool(value)
 
     def enable_experimentation(self) -> None:
         self.experimentation = True
@@ -275,6 +289,43 @@ class AudioRenderer:
         check(lib().arx_get_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in ArxStats._fields_}
 
+    # -- room-acoustic parameters (no reference counterpart) ------------------------
+    def analyze_ir(self) -> None:
+        """arx_analyze_ir: queue the decay curves and ISO 3382-1 parameters of the last started
+        frame's histogram on its stream (asynchronous)."""
+        check(lib().arx_analyze_ir(self._h))
+
+    def set_auto_analyze(self, on: bool) -> None:
+        """arx_set_auto_analyze: every render() queues the analysis behind its IR finalize."""
+        check(lib().arx_set_auto_analyze(self._h, 1 if on else 0))
+
+    def acoustics(self, channel: str | int = "sum") -> dict:
+        """arx_get_acoustics of "left", "right" or "sum" (synchronises): total, unit, edt_s, t20_s,
+        t30_s, c50_db, c80_db, d50, ts_s (NaN where invalid), onset_bin, last_bin, the fit ranges
+        edt_bins / t20_bins / t30_bins, valid (the set of valid quantities' names) and valid_mask."""
+        a = ArxAcoustics()
+        check(lib().arx_get_acoustics(self._h, _channel(channel), C.byref(a)))
+        return _acoustics_dict(a)
+
+    def edc(self, channel: str | int = "sum") -> np.ndarray:
+        """arx_copy_edc: Schroeder's decay curve E[k] = sum of the histogram from bin k on, exact
+        int64 in fixed-point units (times acoustics()["unit"] = energy)."""
+        out = np.empty(self.ir_length, np.int64)
+        check(lib().arx_copy_edc(self._h, _channel(channel), out.ctypes.data_as(C.POINTER(C.c_int64)), out.size))
+        return out
+
+    def analysis_times(self, n: int = 64) -> np.ndarray:
+        """Device ms of the last min(n, ring) analyses, oldest first (arx_analysis_times)."""
+        out = np.zeros(n, np.float64)
+        k = C.c_size_t()
+        check(lib().arx_analysis_times(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), n, C.byref(k)))
+        return out[:k.value]
+
+    def set_scan_shape(self, shape: int) -> None:
+        """Measurement hook (arx_debug_set_scan_shape): 1 = one workgroup per channel, 2 = tiled
+        two-launch scan, 0 = the product's choice; the same bits either way."""
+        check(lib().arx_debug_set_scan_shape(self._h, int(shape)))
+
     # -- convolution ---------------------------------------------------------------
     def convoluteAudioFile(self, samples: np.ndarray) -> tuple[np.ndarray, np.ndarray, float, float]:
         """AudioRenderer::convoluteAudioFile (AudioRenderer.cpp:663-750): host in, host out."""
@@ -333,6 +384,64 @@ class AudioRenderer:
         n = C.c_size_t()
         check(lib().arx_convolute_prepared(self._h, C.c_void_p(d_out_left), C.c_void_p(d_out_right), C.byref(n)))
         return int(n.value)
+
+
+ACOUSTICS_CHANNELS = ("left", "right", "sum")
+
+
+def _channel(channel: str | int) -> int:
+    """A channel's number; an unknown name goes to the library as -1 (rejected)."""
+    if isinstance(channel, str):
+        return ACOUSTICS_CHANNELS.index(channel) if channel in ACOUSTICS_CHANNELS else -1
+    return int(channel)
+
+
+def _acoustics_dict(a: ArxAcoustics) -> dict:
+    d = {}
+    for k, _ in ArxAcoustics._fields_[:-1]:  # not the reserved word
+        v = getattr(a, k)
+        d[k] = tuple(v) if k.endswith("_bins") else v
+    d["valid_mask"] = int(a.valid)
+    d["valid"] = {name for bit, name in enumerate(ACOUSTICS_VALID) if a.valid >> bit & 1}
+    return d
+
+
+def acoustics_from_histogram(left, right, sample_rate: int, unit: float = 1.0) -> dict:
+    """arx_acoustics_from_histogram (host only, no device): the parameters of an int64 histogram
+    pair by the definitions of include/arx.h, as {"left": ..., "right": ..., "sum": ...}."""
+    L = np.ascontiguousarray(left, np.int64)
+    R = np.ascontiguousarray(right, np.int64)
+    if L.shape != R.shape or L.ndim != 1:
+        raise ValueError("left and right must be one-dimensional and of one length")
+    out = (ArxAcoustics * 3)()
+    P = C.POINTER(C.c_int64)
+    check(lib().arx_acoustics_from_histogram(L.ctypes.data_as(P), R.ctypes.data_as(P), L.size, int(sample_rate),
+                                             float(unit), out))
+    return {name: _acoustics_dict(out[i]) for i, name in enumerate(ACOUSTICS_CHANNELS)}
+
+
+def write_acoustics_json(path: str, channels: dict) -> None:
+    """{"left" | "right" | "sum": acoustics()} as JSON: invalid quantities (NaN) as null, an infinite
+    clarity as the string "inf", valid as a sorted list."""
+    def plain(v):
+        if isinstance(v, (set, frozenset)):
+            return sorted(v)
+        if isinstance(v, float) and not np.isfinite(v):
+            return None if np.isnan(v) else ("inf" if v > 0 else "-inf")
+        return list(v) if isinstance(v, tuple) else v
+
+    with open(path, "w") as fh:
+        json.dump({ch: {k: plain(v) for k, v in a.items()} for ch, a in channels.items()}, fh, indent=1)
+        fh.write("\n")
+
+
+def edc_from_histogram(hist) -> np.ndarray:
+    """arx_edc_from_histogram (host only): the reverse inclusive cumulative sum of int64 bins."""
+    h = np.ascontiguousarray(hist, np.int64)
+    out = np.empty(h.size, np.int64)
+    P = C.POINTER(C.c_int64)
+    check(lib().arx_edc_from_histogram(h.ctypes.data_as(P), h.size, out.ctypes.data_as(P)))
+    return out
 
 
 FADE_SHAPES = ("linear", "hann")  # ARX_FADE_LINEAR, ARX_FADE_HANN

@@ -201,6 +201,87 @@ int32_t arx_timing_ring(void);
  * (AudioRenderer.h:27).  arx_get_stats' trace_ms / conv_ms then report the last timed launch. */
 arx_status arx_set_timing(arx_renderer* r, int32_t on);
 
+/* ---- Room-acoustic parameters (ISO 3382-1) of the traced histogram ---------------------------
+ * No reference counterpart: the reference only ever convolves its IR.  Per channel c (0 left ear,
+ * 1 right ear, 2 left + right: the curve of the mono IR), with h[k] >= 0 the histogram bin in
+ * fixed-point units, n = ir_len and sr the sample rate:
+ *   E[k] = sum_{j >= k} h[j], k in [0, n], E[n] = 0: Schroeder's decay curve, exact in int64 (so as
+ *   independent of the GPU count as the histogram); total = E[0].
+ *   onset / last = the first / last bin with h > 0 (-1, -1 when total == 0).
+ *   "E[k] is at or below -x dB" means (double)E[k] <= (double)E[0] * Cx, "at or above" >=, with the
+ *   four f64 literals below -- part of the contract, so the fit ranges are exact integers.
+ *   Fit range [a, b], inclusive.  EDT: a = onset, b = the last bin with E > 0 at or above -10 dB.
+ *   T20: a = the first bin >= onset at or below -5 dB, b = the last bin with E > 0 at or above
+ *   -25 dB.  T30: as T20 with -35 dB.  A range is valid when b - a >= 1; (a, b) = (-1, -1) when no
+ *   such bins exist.
+ *   Fit, centred: x_k = k - (a + b)/2, y_k = 10 log10((double)E[k] / (double)E[0]), slope =
+ *   sum x_k y_k / sum x_k^2 (dB per bin), T = -60 / (slope * sr) seconds, EDT by the same formula on
+ *   its own range.  A time is valid when its range is and slope < 0.
+ *   Windows: n50 = (50 sr + 500) / 1000, n80 = (80 sr + 500) / 1000 (integer division);
+ *   early50 = E[onset] - E[min(onset + n50, n)], late50 = E[min(onset + n50, n)], both exact;
+ *   C50 = 10 log10(early50 / late50), +inf when late50 == 0 and early50 > 0; D50 = early50 / total;
+ *   C80 the same with n80.  C50 / D50 (C80) are valid when n50 (n80) > 0 and total > 0, C50 / C80
+ *   when early > 0 as well.
+ *   Ts = (sum_{k > onset} (k - onset) h[k]) / (total * sr) seconds, the numerator summed in 128 bits
+ *   (it passes 64 for histograms the engine can produce) and converted to f64 once.
+ *   total == 0: every float NaN, every bin -1, valid == 0 (and the status ARX_OK).  Invalid
+ *   quantities are NaN.
+ * The analysis describes the last TRACED histogram (or the attached one), never the f32 IR: an IR
+ * installed with arx_set_ir is not analysed. */
+#define ARX_ACOUSTICS_C5  3.1622776601683794e-01 /* 10^-0.5 */
+#define ARX_ACOUSTICS_C10 1.0000000000000001e-01 /* 0.1 */
+#define ARX_ACOUSTICS_C25 3.1622776601683794e-03 /* 10^-2.5 */
+#define ARX_ACOUSTICS_C35 3.1622776601683794e-04 /* 10^-3.5 */
+#define ARX_VALID_EDT 0x01u
+#define ARX_VALID_T20 0x02u
+#define ARX_VALID_T30 0x04u
+#define ARX_VALID_C50 0x08u
+#define ARX_VALID_C80 0x10u
+#define ARX_VALID_D50 0x20u
+#define ARX_VALID_TS  0x40u
+typedef struct arx_acoustics {
+    int64_t total;              /* E[0], fixed-point units */
+    double unit;                /* energy per unit: e0 * 2^-frac_bits (arx_finalize_ir's) */
+    double edt_s, t20_s, t30_s; /* seconds */
+    double c50_db, c80_db, d50;
+    double ts_s;                /* seconds */
+    int32_t onset_bin, last_bin;
+    int32_t edt_bins[2], t20_bins[2], t30_bins[2]; /* fit ranges [a, b] */
+    uint32_t valid;             /* ARX_VALID_* */
+    uint32_t reserved;          /* 0: the struct's size is a multiple of 8 with no implicit padding */
+} arx_acoustics;
+/* Queue the analysis of the last started frame's histogram (the attached one when there is one) on
+ * that frame's stream: the decay curves of the three channels, then their parameters.
+ * Asynchronous, no host synchronisation (the first analysis of a frame set allocates its buffers).
+ * In a group, call it on a member after arx_group_render: the all-reduced histogram is already
+ * there.  Needs no scene. */
+arx_status arx_analyze_ir(arx_renderer* r);
+/* on != 0: arx_render and arx_group_render queue the analysis right after the IR finalize of every
+ * frame.  Off by default; off, nothing new is launched and no output changes by a bit. */
+arx_status arx_set_auto_analyze(arx_renderer* r, int32_t on);
+/* Channel 0 / 1 / 2 of the last started frame's analysis; synchronises that frame's stream, like
+ * arx_get_stats.  ARX_ERR_NOT_READY when no analysis was queued for that frame. */
+arx_status arx_get_acoustics(arx_renderer* r, int32_t channel, arx_acoustics* out);
+/* The decay curves in device memory: 3*ir_len int64, channel 0, then 1, then 2 (NULL before the
+ * frame set's first analysis). */
+arx_status arx_edc_device(arx_renderer* r, int64_t** d_edc, size_t* n_elems);
+/* One channel's curve to the host; synchronising.  ARX_ERR_NOT_READY like arx_get_acoustics. */
+arx_status arx_copy_edc(arx_renderer* r, int32_t channel, int64_t* h_edc, size_t ir_len);
+/* Device times of the last min(n, arx_timing_ring()) analyses (scan to results), oldest first, like
+ * arx_live_times; obeys arx_set_timing. */
+arx_status arx_analysis_times(arx_renderer* r, double* ms, size_t n, size_t* n_out);
+/* Host only, no device needed: the same definitions in plain C++.  left / right: ir_len bins >= 0
+ * whose sum fits int64 (ARX_ERR_INVALID_ARGUMENT otherwise, and for NULL, ir_len == 0 or
+ * sample_rate <= 0); out[c] = channel c. */
+arx_status arx_acoustics_from_histogram(const int64_t* left, const int64_t* right, size_t ir_len,
+                                        int32_t sample_rate, double unit, arx_acoustics out[3]);
+arx_status arx_edc_from_histogram(const int64_t* hist, size_t ir_len, int64_t* edc);
+/* The decay curve's scan kernels: 0 = the product's choice, 1 = one workgroup per channel (one
+ * launch), 2 = tiled (tile sums, then an apply that adds up the sums above its tile: two launches;
+ * the product's).  Both give the same bits; the first is kept as a measured alternative
+ * (tools/acoustics_time.py). */
+arx_status arx_debug_set_scan_shape(arx_renderer* r, int32_t shape);
+
 /* Identity of the trace kernel compiled into this library: a hash of its sources and experiment
  * macros (build.py trace_source_id).  Stored PMC profiles carry it with the tree hash and VGPR
  * count, and bench.py uses a stored profile only when all three match its own run.  No
