@@ -1,0 +1,806 @@
+// arx_capi_trace.cpp -- one frame behind the C ABI (include/arx.h): the receiver model and the
+// device scene, the trace launch, the IR's finalize and its room-acoustic analysis, and the arx_debug_*
+// entry points of the trace.
+//
+// Host-side counterpart of R/prebuild/obj_raytracer/AudioRenderer.cpp (buildAccel, buildSBT, reload,
+// render), re-designed for HIP: persistent device buffers, and no full rebuild when the listener moves.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "arx_internal.hpp"
+
+using namespace arx;
+
+#ifndef ARX_TRACE_PROF
+#define ARX_TRACE_PROF 0  // measurement builds only (build.py --exp TAG -D ARX_TRACE_PROF=1)
+#endif
+
+namespace {
+
+float initial_energy(const arx_config& c) {
+    // devicePrograms.cu:208 -- (x*y*z) is an int product in the reference
+    const int32_t n = c.rays_x * c.rays_y * c.rays_z;
+    return (float)((double)c.base_power / ((double)n * 4.18879020478));
+}
+
+// OptixModel.cpp:178-193 (glm::rotate(mat4(1), -radians(yaw), +Y) * v, then + camera),
+// restated with glm's exact operation order (matrix_transform.inl rotate, type_mat4x4.inl
+// operator*): x' = (c*x + R10*y) + (s*z + 0), y' = (0*x + R11*y) + (0*z + 0),
+// z' = (-s*x + 0*y) + (c*z + 0) with c = cos(-a), s = sin(-a), R11 = c + (1 - c).
+void place_vertices(const float* local, int64_t n_vertices, float x, float y, float z, float yaw_deg, float* out) {
+    const float ang = yaw_deg * static_cast<float>(0.01745329251994329576923690768489);  // glm::radians
+    const float a = -ang;
+    const float c = std::cos(a);
+    const float s = std::sin(a);
+    const float t1 = 1.0f - c;   // temp = (1 - c) * axis, axis = (0, 1, 0)
+    const float r00 = c + 0.0f * 0.0f;
+    const float r10 = t1 * 0.0f - s * 0.0f;
+    const float r20 = 0.0f * 0.0f + s * 1.0f;
+    const float r01 = 0.0f * 1.0f + s * 0.0f;
+    const float r11 = c + t1 * 1.0f;
+    const float r21 = 0.0f * 1.0f - s * 0.0f;
+    const float r02 = 0.0f * 0.0f - s * 1.0f;
+    const float r12 = t1 * 0.0f + s * 0.0f;
+    const float r22 = c + 0.0f * 0.0f;
+    for (int64_t i = 0; i < n_vertices; ++i) {
+        const float vx = local[3 * i + 0], vy = local[3 * i + 1], vz = local[3 * i + 2];
+        const float ox = (r00 * vx + r10 * vy) + (r20 * vz + 0.0f * 1.0f);
+        const float oy = (r01 * vx + r11 * vy) + (r21 * vz + 0.0f * 1.0f);
+        const float oz = (r02 * vx + r12 * vy) + (r22 * vz + 0.0f * 1.0f);
+        out[3 * i + 0] = x + ox;
+        out[3 * i + 1] = y + oy;
+        out[3 * i + 2] = z + oz;
+    }
+}
+
+// Rotation of place_vertices (row-major r00 r10 r20 / r01 r11 r21 / r02 r12 r22), exactly its floats.
+void receiver_rotation(float yaw_deg, float m[9]) {
+    const float ang = yaw_deg * static_cast<float>(0.01745329251994329576923690768489);
+    const float a = -ang, c = std::cos(a), s = std::sin(a), t1 = 1.0f - c;
+    m[0] = c + 0.0f * 0.0f; m[1] = t1 * 0.0f - s * 0.0f; m[2] = 0.0f * 0.0f + s * 1.0f;
+    m[3] = 0.0f * 1.0f + s * 0.0f; m[4] = c + t1 * 1.0f; m[5] = 0.0f * 1.0f - s * 0.0f;
+    m[6] = 0.0f * 0.0f - s * 1.0f; m[7] = t1 * 0.0f + s * 0.0f; m[8] = c + 0.0f * 0.0f;
+}
+
+// The receiver sub-tree, built once in the receiver's local frame whenever the receiver model or
+// the scene changes (its triangle ids and offsets follow the scene); listener moves refit it on
+// the device (arx_receiver.hip).  Larger receivers than the refit kernel's LDS holds are rebuilt on
+// the host per move instead (recv_refit = false).
+arx_status prepare_receiver_model(arx_renderer* r) {
+    std::vector<float> tv, ab;
+    float radius = 0.0f;
+    for (int side = 0; side < 2; ++side) {
+        const std::vector<float>& loc = r->recv_local[side];
+        tv.insert(tv.end(), loc.begin(), loc.end());
+        ab.insert(ab.end(), loc.size() / 9, side == 0 ? -1.0f : -2.0f);
+        for (size_t i = 0; i + 2 < loc.size(); i += 3)
+            radius = std::max(radius, std::sqrt(loc[i] * loc[i] + loc[i + 1] * loc[i + 1] + loc[i + 2] * loc[i + 2]));
+    }
+    const int64_t n = (int64_t)ab.size();
+    r->recv_refit = n <= kRefitMaxTris;
+    r->recv_radius = radius * 1.0001f + 1e-6f;  // |R v| = |v|: the rotated halves stay in this ball
+    if (!r->recv_refit) return ARX_OK;
+    const BvhBuild& sc = r->scene_img->bvh;
+    build_bvh(tv.data(), ab.data(), 0.0f, n, (int32_t)r->scene_img->n_input, r->recv);
+    relocate_bvh(r->recv, 1 + (int32_t)sc.nodes.size(), (int32_t)sc.tris.size());
+    const char* why = "";
+    const size_t total_nodes = 1 + sc.nodes.size() + r->recv.nodes.size();
+    const size_t total_tris = sc.tris.size() + r->recv.tris.size();
+    if (!validate_bvh_range(r->recv.nodes.data(), 1 + sc.nodes.size(), r->recv.nodes.size(), total_nodes,
+                            total_tris, &why))
+        return fail(ARX_ERR_INTERNAL, "BVH validation failed (receiver): %s", why);
+    // refit schedule: inner nodes by depth, deepest level first
+    const int32_t base = 1 + (int32_t)sc.nodes.size();
+    std::vector<int32_t> depth(r->recv.nodes.size(), 0);
+    int32_t max_d = 0;
+    for (size_t i = 0; i < r->recv.nodes.size(); ++i)  // parents precede children (pre-order)
+        for (int c = 0; c < 2; ++c)
+            if (r->recv.nodes[i].d[2 + c] == 0) {
+                const int32_t ch = r->recv.nodes[i].d[c] - base;
+                depth[(size_t)ch] = depth[i] + 1;
+                max_d = std::max(max_d, depth[(size_t)ch]);
+            }
+    std::vector<int32_t> order, start;
+    for (int32_t d = max_d; d >= 0 && !r->recv.nodes.empty(); --d) {
+        start.push_back((int32_t)order.size());
+        for (size_t i = 0; i < r->recv.nodes.size(); ++i)
+            if (depth[i] == d) order.push_back((int32_t)i);
+    }
+    start.push_back((int32_t)order.size());
+    r->recv_levels = r->recv.nodes.empty() ? 0 : (int32_t)start.size() - 1;
+    if (receiver_refit_lds((int32_t)r->recv.tris.size(), (int32_t)r->recv.nodes.size(), r->recv_levels) > 160 * 1024) {
+        r->recv_refit = false;  // beyond one workgroup's LDS: rebuilt on the host per move instead
+        return ARX_OK;
+    }
+    hipFree(r->d_recv_local);
+    hipFree(r->d_recv_nodes);
+    hipFree(r->d_recv_levels);
+    r->d_recv_local = nullptr;
+    r->d_recv_nodes = nullptr;
+    r->d_recv_levels = nullptr;
+    ARX_HIP(hipMalloc(&r->d_recv_local, std::max<size_t>(1, r->recv.tris.size()) * sizeof(TriRec)));
+    ARX_HIP(hipMalloc(&r->d_recv_nodes, std::max<size_t>(1, r->recv.nodes.size()) * sizeof(BvhNode)));
+    ARX_HIP(hipMalloc(&r->d_recv_levels, (order.size() + start.size()) * sizeof(int32_t)));
+    if (!r->recv.tris.empty())
+        ARX_HIP(hipMemcpyAsync(r->d_recv_local, r->recv.tris.data(), r->recv.tris.size() * sizeof(TriRec),
+                               hipMemcpyHostToDevice, r->stream));
+    if (!r->recv.nodes.empty())
+        ARX_HIP(hipMemcpyAsync(r->d_recv_nodes, r->recv.nodes.data(), r->recv.nodes.size() * sizeof(BvhNode),
+                               hipMemcpyHostToDevice, r->stream));
+    std::vector<int32_t> lv(order);
+    lv.insert(lv.end(), start.begin(), start.end());
+    ARX_HIP(hipMemcpyAsync(r->d_recv_levels, lv.data(), lv.size() * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
+    ARX_HIP(hipStreamSynchronize(r->stream));  // pageable sources
+    r->recv_level_count = (int32_t)order.size();
+    if (!r->use_w4) return ARX_OK;
+    // opt-in CW4 path only: the receiver's CW4 layout (root at unit kW4RecvRoot, blocks after the
+    // scene's) for the refit
+    collapse_w4(r->recv, base, (int32_t)sc.tris.size(), r->recv.root, kW4RecvRoot, r->scene_img->wide().w4.unit_end,
+                r->recv4);
+    std::vector<int32_t> w4n(11 * r->recv4.nodes.size()), w4t(2 * r->recv4.leaf_tris.size());
+    for (size_t i = 0; i < r->recv4.nodes.size(); ++i) {
+        std::copy(r->recv4.src.begin() + 8 * i, r->recv4.src.begin() + 8 * i + 8, w4n.begin() + 11 * i);
+        w4n[11 * i + 8] = (int32_t)r->recv4.nodes[i].meta;
+        w4n[11 * i + 9] = (int32_t)r->recv4.nodes[i].base;
+        w4n[11 * i + 10] = (int32_t)r->recv4.nodes[i].self;
+    }
+    for (size_t i = 0; i < r->recv4.leaf_tris.size(); ++i) {
+        w4t[2 * i] = (int32_t)r->recv4.leaf_tris[i].first;
+        w4t[2 * i + 1] = r->recv4.leaf_tris[i].second;
+    }
+    hipFree(r->d_recv_w4);
+    hipFree(r->d_recv_w4_tris);
+    r->d_recv_w4 = nullptr;
+    r->d_recv_w4_tris = nullptr;
+    ARX_HIP(hipMalloc(&r->d_recv_w4, std::max<size_t>(1, w4n.size()) * sizeof(int32_t)));
+    ARX_HIP(hipMalloc(&r->d_recv_w4_tris, std::max<size_t>(1, w4t.size()) * sizeof(int32_t)));
+    if (!w4n.empty())
+        ARX_HIP(hipMemcpyAsync(r->d_recv_w4, w4n.data(), w4n.size() * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
+    if (!w4t.empty())
+        ARX_HIP(hipMemcpyAsync(r->d_recv_w4_tris, w4t.data(), w4t.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                               r->stream));
+    ARX_HIP(hipStreamSynchronize(r->stream));  // pageable sources
+    return ARX_OK;
+}
+
+// Box padding of the refit kernel (RefitArgs::pad): at least the builder's 1e-5 * max|coordinate|
+// for any vertex of the placed receiver (|v| <= |center| + radius).
+float refit_pad(const arx_renderer* r) {
+    float mx = 0.0f;
+    for (int k = 0; k < 3; ++k) mx = std::max(mx, std::fabs(r->center[k]));
+    return std::max(1e-5f * (mx + r->recv_radius) * 1.001f, 1e-6f);
+}
+
+// World-space bound of the placed receiver (for the quantization grid): the refit path's ball
+// widened by the refit kernel's box padding (the padded boxes it quantizes must stay on the grid),
+// or the host-built sub-tree's root box.
+void receiver_bound(const arx_renderer* r, float lo[3], float hi[3], bool* empty) {
+    *empty = (r->recv_local[0].size() + r->recv_local[1].size()) == 0;
+    const float pad = r->recv_refit ? refit_pad(r) : 0.0f;
+    for (int k = 0; k < 3; ++k) {
+        if (r->recv_refit) {
+            lo[k] = r->center[k] - r->recv_radius - 2.0f * pad;
+            hi[k] = r->center[k] + r->recv_radius + 2.0f * pad;
+        } else {
+            lo[k] = r->recv.root.lo[k];
+            hi[k] = r->recv.root.hi[k];
+        }
+    }
+}
+
+arx_status ensure_device_scene(arx_renderer* r) {
+    if (!r->scene_img) return fail(ARX_ERR_NOT_READY, "arx_set_scene has not been called");
+    const bool writes = r->scene_dirty || r->recv_model_dirty || r->recv_pose_dirty || !r->qgrid_set;
+    if (writes) {
+        // the uploads, re-quantization and receiver refit below write the tree the other frame in
+        // flight may still be tracing
+        const arx_status st = fif_wait_traced(r);
+        if (st != ARX_OK) return st;
+        ++r->tree_gen;  // this write's off-grid flag value (arx_renderer::d_tree_flag)
+    }
+    const SceneImage& img = *r->scene_img;
+    const BvhBuild& sc = img.bvh;
+    const bool model_changed = r->recv_model_dirty || r->scene_dirty;
+    if (model_changed) {
+        arx_status st = prepare_receiver_model(r);
+        if (st != ARX_OK) return st;
+    }
+    const bool pose_changed = model_changed || r->recv_pose_dirty;
+    if (!r->recv_refit && pose_changed) {
+        // host path (receivers beyond the refit kernel's capacity): receiver halves placed in world
+        // space, left then right (placeReceiver OptixModel.cpp:153-157), sub-tree rebuilt
+        std::vector<float> tv;
+        std::vector<float> ab;
+        for (int side = 0; side < 2; ++side) {
+            const std::vector<float>& loc = r->recv_local[side];
+            const int64_t nt = (int64_t)loc.size() / 9;
+            size_t base = tv.size();
+            tv.resize(base + loc.size());
+            place_vertices(loc.data(), 3 * nt, r->center[0], r->center[1], r->center[2], r->yaw, tv.data() + base);
+            ab.insert(ab.end(), (size_t)nt, side == 0 ? -1.0f : -2.0f);
+        }
+        build_bvh(tv.data(), ab.data(), 0.0f, (int64_t)ab.size(), (int32_t)img.n_input, r->recv);
+        relocate_bvh(r->recv, 1 + (int32_t)sc.nodes.size(), (int32_t)sc.tris.size());
+        if (r->use_w4)
+            collapse_w4(r->recv, 1 + (int32_t)sc.nodes.size(), (int32_t)sc.tris.size(), r->recv.root, kW4RecvRoot,
+                        img.wide().w4.unit_end, r->recv4);
+    }
+    const size_t n_nodes = 1 + sc.nodes.size() + r->recv.nodes.size();
+    const size_t n_tris = sc.tris.size() + r->recv.tris.size();
+    arx_status fit = check_buffer_offsets(n_nodes, n_tris);
+    if (fit != ARX_OK) return fit;
+    bool full = r->scene_dirty;
+    if (n_nodes > r->nodes_cap) {
+        if (r->d_cnodes) ARX_HIP(hipFree(r->d_cnodes));
+        if (r->d_qnodes) ARX_HIP(hipFree(r->d_qnodes));
+        r->d_cnodes = nullptr;
+        r->d_qnodes = nullptr;
+        size_t cap = n_nodes + 1024;
+        ARX_HIP(hipMalloc(&r->d_cnodes, cap * sizeof(BvhNode)));
+        ARX_HIP(hipMalloc(&r->d_qnodes, cap * sizeof(QNode2)));
+        r->nodes_cap = cap;
+        full = true;
+    }
+    if (n_tris > r->tris_cap || r->d_tris == nullptr) {
+        if (r->d_tris) ARX_HIP(hipFree(r->d_tris));
+        r->d_tris = nullptr;
+        size_t cap = std::max<size_t>(n_tris + 4096, 1);
+        ARX_HIP(hipMalloc(&r->d_tris, cap * sizeof(TriRec)));
+        r->tris_cap = cap;
+        full = true;
+    }
+    // CW4 (opt-in, use_w4 only): the buffer holds the scene's units, then the receiver's; the f32
+    // records are the top node, the scene's nodes and (host-built receivers) the receiver's
+    static const SceneImage::Wide kNoWide;
+    const SceneImage::Wide& wide = r->use_w4 ? img.wide() : kNoWide;
+    const size_t w_units = r->use_w4 ? std::max<size_t>(r->recv4.unit_end, wide.w4.unit_end) : 0;
+    const size_t host_recv_w4 = (r->recv_refit || !r->use_w4) ? 0 : r->recv4.nodes.size();
+    const size_t n_w4f = r->use_w4 ? 1 + wide.w4.nodes.size() + host_recv_w4 : 0;
+    if (w_units > r->wbuf_cap) {
+        if (r->d_wbuf) ARX_HIP(hipFree(r->d_wbuf));
+        r->d_wbuf = nullptr;
+        const size_t cap = w_units + 4096;
+        ARX_HIP(hipMalloc(&r->d_wbuf, cap * 16));
+        r->wbuf_cap = cap;
+        full = true;
+    }
+    if (n_w4f > r->w4f_cap) {
+        if (r->d_w4f) ARX_HIP(hipFree(r->d_w4f));
+        r->d_w4f = nullptr;
+        const size_t cap = n_w4f + 1024;
+        ARX_HIP(hipMalloc(&r->d_w4f, cap * sizeof(W4NodeF)));
+        r->w4f_cap = cap;
+        full = true;
+    }
+    r->n_w4f = n_w4f;
+    // The quantization grid: made when the scene changes, grown when the receiver leaves it (a
+    // listener walking out of the room): the new grid spans the old one, the scene, the receiver
+    // and the emitter with half the extent as margin, so such a walk re-grids once or twice, not
+    // per frame.  Either way the quantized copy is re-made on the device from the coded nodes
+    // (launch_requant16): no host quantization, no upload, no synchronisation inside a frame.  An
+    // emitter off the grid (checked per launch, arx_trace_rays) makes that launch take the f32 nodes.
+    float rlo[3], rhi[3];
+    bool recv_empty = false;
+    receiver_bound(r, rlo, rhi, &recv_empty);
+    const bool grow = !full && r->qgrid_set && pose_changed && !recv_empty && !qgrid_contains(r->qgrid, rlo, rhi);
+    const bool regrid = full || !r->qgrid_set || grow;
+    if (regrid) {
+        float lo[3], hi[3];
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = hi[k] = r->emitter[k];
+            if (sc.root.count >= 0) {
+                lo[k] = std::min(lo[k], sc.root.lo[k]);
+                hi[k] = std::max(hi[k], sc.root.hi[k]);
+            }
+            if (!recv_empty) {
+                lo[k] = std::min(lo[k], rlo[k]);
+                hi[k] = std::max(hi[k], rhi[k]);
+            }
+            if (grow) {
+                lo[k] = std::min(lo[k], r->qgrid.origin[k]);
+                hi[k] = std::max(hi[k], r->qgrid.origin[k] + 65000.0f * r->qgrid.scale[k]);
+            }
+        }
+        r->qgrid = make_qgrid(lo, hi, grow ? 0.5 : 0.1);
+        r->qgrid_set = true;
+    }
+    const bool host_recv = !r->recv_refit;
+    const bool top_changed = full || model_changed || (host_recv && pose_changed);
+    if (full || top_changed) {
+        // host uploads, only when the scene or the receiver model changed, or on the host-receiver
+        // path: the top node (its receiver child comes from the refit kernel on the refit path),
+        // the scene's coded nodes and triangles, the receiver part on the host path
+        BvhNode top = make_node(sc.root, host_recv ? r->recv.root : empty_child());
+        const char* why = "";
+        if ((host_recv && !validate_bvh_range(r->recv.nodes.data(), 1 + sc.nodes.size(), r->recv.nodes.size(), n_nodes,
+                                              n_tris, &why)) ||
+            !validate_bvh_range(&top, 0, 1, n_nodes, n_tris, &why))
+            return fail(ARX_ERR_INTERNAL, "BVH validation failed: %s", why);
+        BvhNode ctop;  // pageable sources below live until the synchronisation at the end of this block
+        code_nodes(&top, 1, &ctop);
+        std::vector<BvhNode> crecv(host_recv ? r->recv.nodes.size() : 0);
+        if (host_recv) code_nodes(r->recv.nodes.data(), r->recv.nodes.size(), crecv.data());
+        ARX_HIP(hipMemcpyAsync(r->d_cnodes, &ctop, sizeof(BvhNode), hipMemcpyHostToDevice, r->stream));
+        if (full && !img.coded.empty())
+            ARX_HIP(hipMemcpyAsync(r->d_cnodes + 1, img.coded.data(), img.coded.size() * sizeof(BvhNode),
+                                   hipMemcpyHostToDevice, r->stream));
+        if (full && !sc.tris.empty())
+            ARX_HIP(hipMemcpyAsync(r->d_tris, sc.tris.data(), sc.tris.size() * sizeof(TriRec), hipMemcpyHostToDevice,
+                                   r->stream));
+        if (host_recv && !crecv.empty())
+            ARX_HIP(hipMemcpyAsync(r->d_cnodes + 1 + sc.nodes.size(), crecv.data(), crecv.size() * sizeof(BvhNode),
+                                   hipMemcpyHostToDevice, r->stream));
+        if (host_recv && !r->recv.tris.empty())
+            ARX_HIP(hipMemcpyAsync(r->d_tris + sc.tris.size(), r->recv.tris.data(), r->recv.tris.size() * sizeof(TriRec),
+                                   hipMemcpyHostToDevice, r->stream));
+        // CW4 (opt-in): the scene's buffer image and node records once per scene; the top node's
+        // record (child 0 the scene root, child 1 the host-built receiver's root or, on the refit
+        // path, a placeholder the refit kernel replaces); a host-built receiver's records and triangles
+        std::vector<uint32_t> rimage;
+        if (r->use_w4) {
+            W4NodeF wtop;
+            std::memset(&wtop, 0, sizeof(wtop));
+            wtop.base = kW4SceneRoot;
+            wtop.self = 0;
+            if (sc.root.count >= 0) {
+                wtop.meta |= 1u;
+                for (int k = 0; k < 3; ++k) {
+                    wtop.lo[0][k] = sc.root.lo[k];
+                    wtop.hi[0][k] = sc.root.hi[k];
+                }
+            }
+            if (host_recv && r->recv.root.count >= 0) {
+                wtop.meta |= 1u << 2;
+                for (int k = 0; k < 3; ++k) {
+                    wtop.lo[1][k] = r->recv.root.lo[k];
+                    wtop.hi[1][k] = r->recv.root.hi[k];
+                }
+            }
+            ARX_HIP(hipMemcpyAsync(r->d_w4f, &wtop, sizeof(W4NodeF), hipMemcpyHostToDevice, r->stream));
+            if (full && !wide.wimage.empty())
+                ARX_HIP(hipMemcpyAsync(r->d_wbuf, wide.wimage.data(), wide.wimage.size() * sizeof(uint32_t),
+                                       hipMemcpyHostToDevice, r->stream));
+            if (full && !wide.w4.nodes.empty())
+                ARX_HIP(hipMemcpyAsync(r->d_w4f + 1, wide.w4.nodes.data(), wide.w4.nodes.size() * sizeof(W4NodeF),
+                                       hipMemcpyHostToDevice, r->stream));
+            if (host_recv) {
+                if (!r->recv4.nodes.empty())
+                    ARX_HIP(hipMemcpyAsync(r->d_w4f + 1 + wide.w4.nodes.size(), r->recv4.nodes.data(),
+                                           r->recv4.nodes.size() * sizeof(W4NodeF), hipMemcpyHostToDevice, r->stream));
+                const size_t u0 = wide.w4.unit_end;
+                rimage.assign((r->recv4.unit_end - u0) * 4, 0u);
+                for (const auto& lt : r->recv4.leaf_tris)
+                    std::memcpy(rimage.data() + (size_t)(lt.first - u0) * 4, &r->recv.tris[(size_t)lt.second], sizeof(TriRec));
+                if (!rimage.empty())
+                    ARX_HIP(hipMemcpyAsync(r->d_wbuf + u0, rimage.data(), rimage.size() * sizeof(uint32_t),
+                                           hipMemcpyHostToDevice, r->stream));
+            }
+        }
+        ARX_HIP(hipStreamSynchronize(r->stream));
+    }
+    if (regrid || top_changed) {
+        // the quantized copy of the top node and the scene (and the host-built receiver) from the
+        // coded nodes on the device; on the refit path the refit below writes the receiver's
+        // quantized nodes itself (its coded ones may not exist yet)
+        const size_t nq = host_recv ? n_nodes : 1 + sc.nodes.size();
+        ARX_HIP(launch_requant16(r->d_cnodes, nq, r->qgrid, r->d_qnodes, r->d_tree_flag, r->tree_gen, r->stream));
+        if (r->use_w4)
+            ARX_HIP(launch_requant_w4(r->d_w4f, r->n_w4f, r->qgrid, r->d_wbuf, r->d_tree_flag, r->tree_gen, r->stream));
+        ++r->requants;
+    }
+    r->q_valid = recv_empty || qgrid_contains(r->qgrid, rlo, rhi);
+    if (r->recv_refit && (pose_changed || full || regrid)) {
+        // the listener move itself: one kernel, no host copies, no synchronisation
+        RefitArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.local_tris = r->d_recv_local;
+        a.n_tris = (int32_t)r->recv.tris.size();
+        a.tri_base = (int32_t)sc.tris.size();
+        a.local_nodes = r->d_recv_nodes;
+        a.n_nodes = (int32_t)r->recv.nodes.size();
+        a.node_base = 1 + (int32_t)sc.nodes.size();
+        a.level_nodes = r->d_recv_levels;
+        a.level_start = r->d_recv_levels + r->recv_level_count;
+        a.n_levels = r->recv_levels;
+        a.root_ref = r->recv.root.ref;
+        a.root_count = r->recv.root.count;
+        receiver_rotation(r->yaw, a.m);
+        for (int k = 0; k < 3; ++k) a.t[k] = r->center[k];
+        // >= the builder's pad; receiver_bound covers it (a debug pad does not: the off-grid test)
+        a.pad = r->debug_refit_pad > 0.0f ? r->debug_refit_pad : refit_pad(r);
+        a.grid = r->qgrid;
+        a.tris = r->d_tris;
+        a.cnodes = r->d_cnodes;
+        a.qnodes = r->q_valid ? r->d_qnodes : nullptr;
+        a.flag = r->d_tree_flag;
+        a.flag_value = r->tree_gen;
+        if (r->q_valid && r->use_w4) {  // the opt-in CW4 copy follows the quantized one (same grid)
+            a.wbuf = r->d_wbuf;
+            a.w4_nodes = r->d_recv_w4;
+            a.n_w4 = (int32_t)r->recv4.nodes.size();
+            a.w4_tris = r->d_recv_w4_tris;
+            a.n_w4_tris = (int32_t)r->recv4.leaf_tris.size();
+            a.scene_nonempty = sc.root.count >= 0 ? 1 : 0;
+            for (int k = 0; k < 3; ++k) {
+                a.scene_lo[k] = sc.root.lo[k];
+                a.scene_hi[k] = sc.root.hi[k];
+            }
+        }
+        if (a.n_tris > 0) ARX_HIP(launch_receiver_refit(a, r->stream));
+    }
+    r->scene_dirty = false;
+    r->recv_model_dirty = false;
+    r->recv_pose_dirty = false;
+    if (writes) {  // the other frame set's next trace waits for these writes
+        const arx_status st = fif_done_scene(r);
+        if (st != ARX_OK) return st;
+    }
+    r->stats.n_scene_tris = img.n_input;
+    r->stats.n_receiver_tris = (int64_t)r->recv.tris.size();
+    r->stats.n_nodes = (int64_t)n_nodes;
+    r->stats.bvh_depth = 1 + std::max(sc.depth, r->recv.depth);
+    r->stats.tree_hash = img.hash;
+    r->depth4 = r->use_w4 ? 1 + std::max(wide.w4.depth, r->recv4.depth) : 0;
+    return ARX_OK;
+}
+
+}  // namespace
+
+arx_status arx::set_scene_image(arx_renderer* r, SceneRef img) {
+    const char* why = "";
+    const BvhBuild& b = img->bvh;
+    const arx_status fit = check_buffer_offsets(1 + b.nodes.size(), b.tris.size());
+    if (fit != ARX_OK) return fit;
+    if (!validate_bvh_range(b.nodes.data(), 1, b.nodes.size(), 1 + b.nodes.size(), b.tris.size(), &why))
+        return fail(ARX_ERR_INTERNAL, "BVH validation failed (scene): %s", why);
+    r->scene_img = std::move(img);
+    r->scene_dirty = true;
+    r->recv_model_dirty = true;  // receiver ids and offsets follow the scene
+    return ARX_OK;
+}
+
+arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end, bool timed, bool clear) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    if (ray_end < ray_begin) return fail(ARX_ERR_INVALID_ARGUMENT, "ray_end < ray_begin");
+    // global ray ids index the launch of N = x*y*z rays: energies are normalised by N and the
+    // int64 fixed point's headroom (arx_frac_bits) assumes at most N rays per histogram
+    if (ray_end > n_rays(r->cfg))
+        return fail(ARX_ERR_INVALID_ARGUMENT, "ray_end %llu exceeds the launch's %llu rays", (unsigned long long)ray_end,
+                    (unsigned long long)n_rays(r->cfg));
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    arx_status st = ensure_device_scene(r);
+    if (st != ARX_OK) return st;
+    arx_renderer::FrameSet& f = r->cur();
+    const arx_config& c = r->cfg;
+    TraceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.cnodes = r->d_cnodes;
+    // quantized nodes only while the emitter (the one ray origin off the geometry) is on the
+    // grid: the slab arithmetic's error bound assumes origins within the grid's extent
+    const float* em = r->emitter;
+    a.qnodes = (r->q_valid && !r->force_f32_nodes && qgrid_contains(r->qgrid, em, em)) ? r->d_qnodes : nullptr;
+    // the CW4 tree on the same condition when asked for (arx_debug_set_trace_path bit 3; measured
+    // 1.9x slower than the BVH2 on C3: DESIGN.md section 6.3)
+    a.wbuf = (a.qnodes && r->use_w4 && !r->force_global_stack) ? r->d_wbuf : nullptr;
+    a.qgrid = r->qgrid;
+    a.tris = r->d_tris;
+    a.hist = r->hist();
+    a.counters = f.d_counters;
+    a.cursor = f.d_counters + kCursor;
+    a.seed = c.seed;
+    a.ray_begin = ray_begin;
+    a.ray_end = ray_end;
+    for (int k = 0; k < 3; ++k) {
+        a.emitter[k] = r->emitter[k];
+        a.center[k] = r->center[k];
+    }
+    a.e0 = initial_energy(c);
+    a.inv_unit = (a.e0 != 0.0f) ? std::ldexp(1.0, arx_frac_bits(n_rays(c))) / (double)a.e0 : 0.0;
+    a.energy_thres = c.energy_thres;
+    a.hrtf = c.hrtf_absorption_rate;
+    int32_t secs = r->ir_len / c.sample_rate;  // devicePrograms.cu:227-228
+    secs = std::max(1, std::min(secs, 999));
+    a.dist_limit = (float)(secs * kSpeedOfSound + 1);
+    a.max_bounces = c.max_bounces;
+    a.sample_rate = c.sample_rate;
+    a.ir_len = r->ir_len;
+    a.delay = (int32_t)((double)c.sample_rate * 0.00044);  // devicePrograms.cu:125
+    a.is_mono = c.is_mono;
+    a.bvh_depth = r->stats.bvh_depth;
+    if (clear) {
+        a.clear_bins = 2 * (uint64_t)r->ir_len;
+        a.clear_counters = kCounters;
+    }
+    if (ray_end == ray_begin) {  // nothing to trace: the clear alone
+        if (clear) ARX_HIP(launch_clear(r->hist(), 2 * (uint64_t)r->ir_len, f.d_counters, (int)kCounters, r->stream));
+        return ARX_OK;
+    }
+    if (ray_end - ray_begin > f.dirs_cap) {  // direction pre-pass buffer
+        if (f.d_dirs) ARX_HIP(hipFree(f.d_dirs));
+        f.d_dirs = nullptr;
+        f.dirs_cap = 0;
+        ARX_HIP(hipMalloc(&f.d_dirs, (ray_end - ray_begin) * 16));
+        f.dirs_cap = ray_end - ray_begin;
+    }
+    a.dirs = f.d_dirs;
+    const bool gstack = r->force_global_stack || a.bvh_depth + 1 > kLdsStack;
+    // CW4: up to three pushes per level; the rows beyond the LDS rows overflow into a global column
+    const size_t w4_rows = (size_t)std::max(1, 3 * r->depth4 + 3 - kLdsStack);
+    if (gstack || a.wbuf) {  // trees deeper than the LDS stack: one global column of bvh_depth + 1 entries per lane
+        const size_t lanes = trace_max_lanes(r->cus);
+        const size_t need = (a.wbuf ? w4_rows : (size_t)(a.bvh_depth + 1)) * lanes;
+        if (need > r->gstack_cap) {
+            if (r->d_gstack) ARX_HIP(hipFree(r->d_gstack));
+            r->d_gstack = nullptr;
+            r->gstack_cap = 0;
+            ARX_HIP(hipMalloc(&r->d_gstack, need * sizeof(int32_t)));
+            r->gstack_cap = need;
+        }
+        a.gstack = r->d_gstack;
+        a.gstack_lanes = lanes;
+        // one global stack per renderer: with frames in flight, after the other frames' traces
+        if (const arx_status w = fif_wait_traced(r); w != ARX_OK) return w;
+    }
+#if ARX_TRACE_PROF  // measurement builds only: per-wave records (arx_debug_trace_profile)
+    {
+        const size_t words = (size_t)r->cus * 64 * kProfWords;  // >= waves of any trace grid
+        if (!r->d_prof) {
+            ARX_HIP(hipMalloc(&r->d_prof, words * sizeof(unsigned long long)));
+            r->prof_words = words;
+        }
+        ARX_HIP(hipMemsetAsync(r->d_prof, 0, words * sizeof(unsigned long long), r->stream));
+        a.prof = r->d_prof;
+    }
+#endif
+    // frames in flight: after the other frame set's last writes to the tree (its refit, re-gridding
+    // or upload), which this launch reads
+    if (const arx_status w = fif_wait_scene(r); w != ARX_OK) return w;
+    const int fmt = a.wbuf ? kFmtW4 : (a.qnodes ? kFmtQ16 : kFmtF32);
+    // the instance launch_trace takes (ray pool or small launch): the profile guard reads these
+    const int small = trace_uses_small_block(a, r->cus, r->force_global_stack) ? 1 : 0;
+    r->stats.trace_format = fmt;
+    r->stats.trace_vgprs = r->occ[fmt][small][0];
+    r->stats.trace_waves_per_simd = r->occ[fmt][small][1];
+    r->stats.trace_waves_target = r->occ[fmt][small][2];
+    if (timed && (st = r->trace_ring.begin(r->stream)) != ARX_OK) return st;
+    // Frames in flight: a ray-pool launch is sized for half the CUs' wave slots, so the next frame's
+    // launch runs beside it for its whole length instead of only in its tail.  A launch of 1M rays
+    // gives each lane about three rays; the last of them leave the lanes idle one by one, and a wave
+    // holds its slot until its last lane is done (C3 on the full grid: 5.87e9 queries/s at 1M rays
+    // against 7.23e9 at 10M).  Two half grids side by side: C3 2.60 -> 2.44 ms per frame (DESIGN.md
+    // section 6.3, profiles/r06/grid_ab_*.txt); more than half each makes a launch's last blocks wait
+    // for the other's (55 %: 2.9 ms).  One frame in flight keeps the full grid, and so do the traces
+    // on the renderer's one global stack (deep trees, CW4): they wait for every other frame's trace
+    // above, so they never run beside one.
+#ifndef ARX_SHARED_GRID_PCT
+#define ARX_SHARED_GRID_PCT 50  // design experiments only (build.py --exp): other shares
+#endif
+    const bool shared_grid = r->fif >= 2 && !small && !gstack && !a.wbuf;
+    const int grid_cus = shared_grid ? std::max(1, r->cus * ARX_SHARED_GRID_PCT / 100) : r->cus;
+    r->stats.trace_grid_cus = grid_cus;
+    ARX_HIP(launch_trace(a, grid_cus, r->stream, r->force_global_stack));
+    if (timed && (st = r->trace_ring.end(r->stream)) != ARX_OK) return st;
+    return fif_done_traced(r);
+}
+
+extern "C" {
+
+arx_status arx_set_scene(arx_renderer* r, const float* tri_v, const float* tri_abs, int64_t n) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    const arx_status st = check_scene_input(tri_v, tri_abs, n);
+    if (st != ARX_OK) return st;
+    SceneRef img = build_scene_image(tri_v, tri_abs, n);
+    if (!img) return fail(ARX_ERR_OUT_OF_MEMORY, "scene build failed");
+    return set_scene_image(r, std::move(img));
+}
+
+arx_status arx_set_receiver_model(arx_renderer* r, int side, const float* tri_v, int64_t n) {
+    if (!r || side < 0 || side > 1 || n < 0 || (n > 0 && !tri_v))
+        return fail(ARX_ERR_INVALID_ARGUMENT, "bad receiver model arguments");
+    r->recv_local[side].assign(tri_v, tri_v + 9 * n);
+    r->recv_model_dirty = true;
+    return ARX_OK;
+}
+
+arx_status arx_place_receiver_vertices(const float* local_xyz, int64_t n_vertices, float x, float y, float z,
+                                       float yaw_deg, float* out_xyz) {
+    if (n_vertices < 0 || (n_vertices > 0 && (!local_xyz || !out_xyz)))
+        return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
+    place_vertices(local_xyz, n_vertices, x, y, z, yaw_deg, out_xyz);
+    return ARX_OK;
+}
+
+arx_status arx_clear_histogram(arx_renderer* r) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    const arx_status st = arx::begin_frame(r);
+    if (st != ARX_OK) return st;
+    ARX_HIP(launch_clear(r->hist(), 2 * (uint64_t)r->ir_len, r->cur().d_counters, (int)kCounters, r->stream));
+    return ARX_OK;
+}
+
+arx_status arx_trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end) {
+    return r ? arx::trace_rays(r, ray_begin, ray_end, r->timing) : fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+}
+
+arx_status arx_finalize_ir(arx_renderer* r) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    const float e0 = initial_energy(r->cfg);
+    const double unit = std::ldexp((double)e0, -arx_frac_bits(n_rays(r->cfg)));
+    ARX_HIP(launch_finalize_ir((const long long*)r->hist(), r->cur().d_ir, r->cur().d_ir + r->ir_len, r->ir_len, unit,
+                               r->cfg.is_mono, r->stream));
+    r->conv_ir_dirty = true;
+    r->conv_live_ir_dirty = true;
+    ++r->ir_generation;
+    return ARX_OK;
+}
+
+arx_status arx_render(arx_renderer* r, double* render_ms) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+#ifdef ARX_EXP_SEPARATE_CLEAR  // design experiments only: the clear as a launch of its own (round-5 A/B)
+    arx_status st = arx_clear_histogram(r);
+    if (st != ARX_OK) return st;
+    st = arx::trace_rays(r, 0, n_rays(r->cfg), r->timing || render_ms != nullptr, false);
+#else
+    arx_status st = arx::begin_frame(r);  // the clear rides on the direction pre-pass
+    if (st != ARX_OK) return st;
+    st = arx::trace_rays(r, 0, n_rays(r->cfg), r->timing || render_ms != nullptr, true);
+#endif
+    if (st != ARX_OK) return st;
+    st = arx_finalize_ir(r);
+    if (st != ARX_OK) return st;
+    if (r->auto_analyze && (st = arx_analyze_ir(r)) != ARX_OK) return st;
+    if (render_ms) return r->trace_ring.last_ms(true, render_ms);
+    return ARX_OK;
+}
+
+arx_status arx_analyze_ir(arx_renderer* r) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    arx_renderer::Acoustics& a = r->cur().acou;
+    if (!a.d_edc) {  // this frame set's first analysis
+        hipError_t e;
+        if ((e = hipMalloc(&a.d_edc, 3 * (size_t)r->ir_len * sizeof(long long))) != hipSuccess ||
+            (e = hipMalloc(&a.d_res, 3 * sizeof(arx_acoustics))) != hipSuccess ||
+            (e = hipMalloc(&a.d_scratch, acoustics_scratch_bytes())) != hipSuccess) {
+            free_acoustics(a);
+            return fail(e == hipErrorOutOfMemory ? ARX_ERR_OUT_OF_MEMORY : ARX_ERR_HIP, "arx_analyze_ir: %s",
+                        hipGetErrorString(e));
+        }
+    }
+    if (r->timing)
+        if (const arx_status st = r->analysis_ring.begin(r->stream); st != ARX_OK) return st;
+    AcousticsArgs args{};
+    args.hist = (const long long*)r->hist();
+    args.n = r->ir_len;
+    args.sample_rate = r->cfg.sample_rate;
+    args.unit = std::ldexp((double)initial_energy(r->cfg), -arx_frac_bits(n_rays(r->cfg)));
+    args.edc = a.d_edc;
+    args.out = a.d_res;
+    args.scratch = a.d_scratch;
+    args.shape = r->scan_shape == 0 ? kScanDefault : r->scan_shape;
+    ARX_HIP(launch_acoustics(args, r->stream));
+    if (r->timing)
+        if (const arx_status st = r->analysis_ring.end(r->stream); st != ARX_OK) return st;
+    a.queued = true;
+    return ARX_OK;
+}
+
+arx_status arx_set_auto_analyze(arx_renderer* r, int32_t on) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    r->auto_analyze = on != 0;
+    return ARX_OK;
+}
+
+arx_status arx_debug_set_scan_shape(arx_renderer* r, int32_t shape) {
+    if (!r || shape < 0 || shape > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "scan shape: 0, 1 or 2");
+    r->scan_shape = shape;
+    return ARX_OK;
+}
+
+arx_status arx_get_acoustics(arx_renderer* r, int32_t channel, arx_acoustics* out) {
+    if (!r || !out) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (channel < 0 || channel > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "channel %d: 0 left, 1 right, 2 sum", channel);
+    if (!r->cur().acou.queued) return fail(ARX_ERR_NOT_READY, "no analysis was queued for the last frame (arx_analyze_ir)");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    ARX_HIP(hipMemcpyAsync(out, r->cur().acou.d_res + channel, sizeof(arx_acoustics), hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    return ARX_OK;
+}
+
+arx_status arx_edc_device(arx_renderer* r, int64_t** d_edc, size_t* n) {
+    if (!r || !d_edc) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *d_edc = (int64_t*)r->cur().acou.d_edc;
+    if (n) *n = 3 * (size_t)r->ir_len;
+    return ARX_OK;
+}
+
+arx_status arx_copy_edc(arx_renderer* r, int32_t channel, int64_t* h_edc, size_t ir_len) {
+    if (!r || !h_edc) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (channel < 0 || channel > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "channel %d: 0 left, 1 right, 2 sum", channel);
+    if (ir_len != (size_t)r->ir_len) return fail(ARX_ERR_INVALID_ARGUMENT, "ir_len %zu != %d", ir_len, r->ir_len);
+    if (!r->cur().acou.queued) return fail(ARX_ERR_NOT_READY, "no analysis was queued for the last frame (arx_analyze_ir)");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    ARX_HIP(hipMemcpyAsync(h_edc, r->cur().acou.d_edc + (size_t)channel * ir_len, ir_len * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    return ARX_OK;
+}
+
+arx_status arx_debug_trace_counters(arx_renderer* r, uint64_t* out, size_t n) {
+    if (!r || !out || n > (size_t)kCounters) return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    const arx_renderer::FrameSet& f = r->cur();
+    ARX_HIP(hipMemcpyAsync(f.h_counters, f.d_counters, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           r->stream));
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    for (size_t i = 0; i < n; ++i) out[i] = f.h_counters[i];
+    return ARX_OK;
+}
+
+arx_status arx_debug_node_images(arx_renderer* r, void* cnodes, void* qnodes, size_t n_nodes, float* grid,
+                                 uint64_t* requants) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    if (n_nodes > (size_t)r->stats.n_nodes) return fail(ARX_ERR_INVALID_ARGUMENT, "only %lld nodes", (long long)r->stats.n_nodes);
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    if (cnodes && n_nodes) ARX_HIP(hipMemcpy(cnodes, r->d_cnodes, n_nodes * sizeof(BvhNode), hipMemcpyDeviceToHost));
+    if (qnodes && n_nodes) ARX_HIP(hipMemcpy(qnodes, r->d_qnodes, n_nodes * sizeof(QNode2), hipMemcpyDeviceToHost));
+    if (grid)
+        for (int k = 0; k < 3; ++k) {
+            grid[k] = r->qgrid.origin[k];
+            grid[3 + k] = r->qgrid.scale[k];
+        }
+    if (requants) *requants = r->requants;
+    return ARX_OK;
+}
+
+arx_status arx_debug_trace_profile(arx_renderer* r, uint64_t* out, size_t n_words, size_t* n_out) {
+    if (!r || (n_words > 0 && !out)) return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (!r->d_prof) return fail(ARX_ERR_NOT_READY, "not a profiling build (ARX_TRACE_PROF) or no trace yet");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    const size_t k = std::min(n_words, r->prof_words);
+    ARX_HIP(hipMemcpy(out, r->d_prof, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (n_out) *n_out = k;
+    return ARX_OK;
+}
+
+arx_status arx_debug_set_refit_pad(arx_renderer* r, float pad) {
+    if (!r || !(pad >= 0.0f) || !std::isfinite(pad)) return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
+    r->debug_refit_pad = pad;
+    r->recv_pose_dirty = true;  // the next trace refits with it
+    return ARX_OK;
+}
+
+arx_status arx_debug_set_trace_path(arx_renderer* r, int path) {
+    if (!r || path < 0 || path > 15 || (path & 4)) return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
+    r->force_f32_nodes = (path & 1) != 0;
+    r->force_global_stack = (path & 2) != 0;
+    const bool w4 = (path & 8) != 0;
+    if (w4 && !r->use_w4) {  // the opt-in CW4 copy is made and uploaded at the next trace
+        r->scene_dirty = true;
+        r->recv_model_dirty = true;
+    }
+    r->use_w4 = w4;
+    return ARX_OK;
+}
+
+arx_status arx_debug_ray_directions(uint64_t seed, uint64_t first, uint64_t count, float* h_out, int device) {
+    if (count > 0 && !h_out) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL output");
+    if (count == 0) return ARX_OK;
+    ARX_HIP(hipSetDevice(device));
+    float* d = nullptr;
+    ARX_HIP(hipMalloc(&d, 3 * count * sizeof(float)));
+    hipError_t e = launch_ray_directions(seed, first, count, d, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(h_out, d, 3 * count * sizeof(float), hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (e != hipSuccess) return fail(ARX_ERR_HIP, "ray directions: %s", hipGetErrorString(e));
+    return ARX_OK;
+}
+
+}  // extern "C"

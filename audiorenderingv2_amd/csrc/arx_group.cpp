@@ -51,12 +51,7 @@ struct arx_group {
     uint64_t n_coll[3] = {0, 0, 0};
     // per member: HIP events around its histogram all-reduce (recorded when the member's timing is on
     // or render_ms is asked for), a ring like the renderer's trace ring (arx_group_allreduce_times)
-    static constexpr int kRing = 256;
-    struct ArEvents {
-        hipEvent_t e0[kRing] = {}, e1[kRing] = {};
-        uint64_t n = 0;
-    };
-    std::vector<ArEvents> ar;
+    std::vector<EventRing> ar;
 };
 
 namespace {
@@ -83,10 +78,7 @@ void destroy_members(arx_group* g) {
     }
     for (size_t i = 0; i < g->ar.size(); ++i) {
         hipSetDevice(g->members[i]->cfg.device);
-        for (int k = 0; k < arx_group::kRing; ++k) {
-            if (g->ar[i].e0[k]) hipEventDestroy(g->ar[i].e0[k]);
-            if (g->ar[i].e1[k]) hipEventDestroy(g->ar[i].e1[k]);
-        }
+        g->ar[i].destroy();
     }
     g->ar.clear();
     if (g->summed) {
@@ -461,12 +453,8 @@ arx_status arx_group_render(arx_group* g, double* render_ms) {
             if (g->ar.size() != g->members.size()) g->ar.resize(g->members.size());
             for (size_t i = 0; i < g->members.size(); ++i) {
                 arx_renderer* r = g->members[i];
-                arx_group::ArEvents& ev = g->ar[i];
-                const int k = (int)(ev.n % arx_group::kRing);
                 ARX_HIP(hipSetDevice(r->cfg.device));
-                if (!ev.e0[k]) ARX_HIP(hipEventCreateWithFlags(&ev.e0[k], hipEventDisableSystemFence));
-                if (!ev.e1[k]) ARX_HIP(hipEventCreateWithFlags(&ev.e1[k], hipEventDisableSystemFence));
-                ARX_HIP(hipEventRecord(ev.e0[k], r->stream));
+                if (const arx_status st = g->ar[i].begin(r->stream); st != ARX_OK) return st;
             }
         }
         ARX_NCCL(ncclGroupStart());
@@ -484,10 +472,8 @@ arx_status arx_group_render(arx_group* g, double* render_ms) {
         if (timed)
             for (size_t i = 0; i < g->members.size(); ++i) {
                 arx_renderer* r = g->members[i];
-                arx_group::ArEvents& ev = g->ar[i];
                 ARX_HIP(hipSetDevice(r->cfg.device));
-                ARX_HIP(hipEventRecord(ev.e1[(int)(ev.n % arx_group::kRing)], r->stream));
-                ++ev.n;
+                if (const arx_status st = g->ar[i].end(r->stream); st != ARX_OK) return st;
             }
         if (g->out_of_place)  // the sum back into the histogram the finalise reads, before the next frame's
             for (size_t i = 0; i < g->members.size(); ++i) {  // all-reduce may write the receive buffer
@@ -531,7 +517,7 @@ arx_status arx_group_render(arx_group* g, double* render_ms) {
         for (arx_renderer* r : g->members) {
             ARX_HIP(hipSetDevice(r->cfg.device));
             double ms = 0.0;
-            const arx_status st = last_trace_ms(r, true, &ms);
+            const arx_status st = r->trace_ring.last_ms(true, &ms);
             if (st != ARX_OK) return st;
             worst = std::max(worst, ms);
         }
@@ -545,18 +531,8 @@ arx_status arx_group_allreduce_times(arx_group* g, int32_t member, double* ms, s
         return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
     if (n_out) *n_out = 0;
     if ((size_t)member >= g->ar.size()) return ARX_OK;  // no timed all-reduce yet
-    const arx_group::ArEvents& ev = g->ar[(size_t)member];
     ARX_HIP(hipSetDevice(g->members[(size_t)member]->cfg.device));
-    const uint64_t k = std::min<uint64_t>(std::min<uint64_t>(ev.n, (uint64_t)arx_group::kRing), (uint64_t)n);
-    for (uint64_t i = 0; i < k; ++i) {  // oldest of the last k first
-        const int slot = (int)((ev.n - k + i) % arx_group::kRing);
-        ARX_HIP(hipEventSynchronize(ev.e1[slot]));
-        float f = 0.f;
-        ARX_HIP(hipEventElapsedTime(&f, ev.e0[slot], ev.e1[slot]));
-        ms[i] = f;
-    }
-    if (n_out) *n_out = (size_t)k;
-    return ARX_OK;
+    return g->ar[(size_t)member].times(ms, n, n_out);
 }
 
 void arx_group_conv_shard(int32_t sample_rate, uint64_t n_frames, int32_t rank, int32_t n_ranks, uint64_t* begin,
@@ -584,7 +560,7 @@ arx_status arx_group_convolute_device(arx_group* g, const float* const* d_in, si
         uint64_t pb = 0, pe = 0;
         conv_pairs_of(r->cfg.sample_rate, n_frames, g->rank0 + (int32_t)i, g->n_ranks, &pb, &pe);
         const arx_status st = convolute_pairs(r, d_in[i], n_frames, d_out_left[i], d_out_right[i], (int64_t)pb,
-                                              (int64_t)pe);
+                                              (int64_t)pe, r->timing);
         if (st != ARX_OK) return st;
     }
     return ARX_OK;
@@ -609,7 +585,6 @@ arx_status arx_group_convolute_audio_file(arx_group* g, const float* h_in, size_
         }
     } ev;
     const int32_t sr = r0->cfg.sample_rate;
-    std::vector<uint64_t> conv_slot(g->members.size(), 0);
     for (size_t i = 0; i < g->members.size(); ++i) {
         arx_renderer* r = g->members[i];
         const int32_t rank = g->rank0 + (int32_t)i;
@@ -640,11 +615,9 @@ arx_status arx_group_convolute_audio_file(arx_group* g, const float* h_in, size_
         if (in_hi > in_lo)
             ARX_HIP(hipMemcpyAsync(r->d_conv_in + in_lo, h_in + in_lo, (in_hi - in_lo) * sizeof(float),
                                    hipMemcpyHostToDevice, r->stream));
-        const bool timing = r->timing;
-        r->timing = timing || convolute_ms != nullptr;  // the convolution's own window when asked for
-        arx_status st = convolute_pairs(r, r->d_conv_in, n, r->d_conv_out, r->d_conv_out + n, (int64_t)pb, (int64_t)pe);
-        conv_slot[i] = r->conv_launches;
-        r->timing = timing;
+        // timed when asked for the convolution's own window
+        const arx_status st = convolute_pairs(r, r->d_conv_in, n, r->d_conv_out, r->d_conv_out + n, (int64_t)pb,
+                                              (int64_t)pe, r->timing || convolute_ms != nullptr);
         if (st != ARX_OK) return st;
         if (e > b) {  // this rank's output frames back into the caller's buffers
             ARX_HIP(hipMemcpyAsync(h_out_left + b, r->d_conv_out + b, (e - b) * sizeof(float), hipMemcpyDeviceToHost,
@@ -663,10 +636,10 @@ arx_status arx_group_convolute_audio_file(arx_group* g, const float* h_in, size_
         float ms = 0.f;
         ARX_HIP(hipEventElapsedTime(&ms, p0, p1));
         proc = std::max(proc, (double)ms);
-        if (convolute_ms && conv_slot[i] > 0) {
-            const int slot = (int)((conv_slot[i] - 1) % arx_renderer::kTraceRing);
-            ARX_HIP(hipEventElapsedTime(&ms, r->cev0[slot], r->cev1[slot]));
-            conv = std::max(conv, (double)ms);
+        if (convolute_ms && r->conv_ring.launches > 0) {  // each member is a renderer of its own: its last launch
+            double cms = 0.0;
+            if (const arx_status st = r->conv_ring.last_ms(false, &cms); st != ARX_OK) return st;
+            conv = std::max(conv, cms);
         }
     }
     if (convolute_ms) *convolute_ms = conv;

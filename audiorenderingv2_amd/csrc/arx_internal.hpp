@@ -1,5 +1,8 @@
 // arx_internal.hpp -- libarx.so internals shared by the C ABI translation units
-// (arx_capi.cpp: one renderer; arx_group.cpp: ray-sharded multi-GPU groups).
+// (arx_capi.cpp: one renderer's lifecycle, frame sets, timing rings and getters; arx_scene.cpp: the
+// host-only scene image; arx_capi_trace.cpp: a frame -- device scene, trace, finalize, analysis;
+// arx_capi_conv.cpp: the file, live and streaming convolution; arx_group.cpp: ray-sharded multi-GPU
+// groups).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -85,8 +88,22 @@ SceneRef deserialize_scene(const uint8_t* p, size_t n, const char** why);
 struct arx_renderer;
 struct arx_stream;
 namespace arx {
-// Device time (ms) of the renderer's last trace launch; wait = synchronise on it first.
-arx_status last_trace_ms(arx_renderer* r, bool wait, double* ms);
+// A ring of (start, end) event pairs around the last kTraceRing timed launches of one kind.  A launch
+// that is not timed records nothing and does not advance the ring.
+constexpr int kTraceRing = 256;
+struct EventRing {
+    hipEvent_t e0[kTraceRing] = {}, e1[kTraceRing] = {};
+    uint64_t launches = 0;  // timed launches (the ring's index)
+    arx_status create_all();  // every slot's events now (begin makes a slot's on first use otherwise)
+    void destroy();
+    arx_status begin(hipStream_t s);  // the start event of the next launch
+    arx_status end(hipStream_t s);    // its end event; counts the launch
+    // Device time (ms) of the last launch; wait = synchronise on it first.
+    arx_status last_ms(bool wait, double* ms) const;
+    // Device times of the last min(n, ring) launches, oldest first.
+    arx_status times(double* ms, size_t n, size_t* n_out) const;
+};
+
 // arx_trace_rays with the per-launch events recorded or not (arx_set_timing, or a caller asking for the
 // time); clear: the direction pre-pass zeroes the histogram and counters first (render() after
 // begin_frame, instead of arx_clear_histogram's launch)
@@ -95,21 +112,27 @@ arx_status trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end, boo
 arx_status begin_frame(arx_renderer* r);
 // Install a built scene (arx_set_scene's second half): uploaded at the next trace.
 arx_status set_scene_image(arx_renderer* r, SceneRef img);
-// Frames in flight (arx_set_frames_in_flight): the current set's stream waits for the other set's
-// last trace / convolution / all-reduce (no-ops with one frame in flight); `done_*` record the
-// current set's.
+// Frames in flight (arx_set_frames_in_flight; no-ops with one): the current set's stream waits for
+// every other set's last trace / for the set that did the last scene write, convolution or all-reduce;
+// `done_*` record the current set's.
 arx_status fif_wait_traced(arx_renderer* r);
+arx_status fif_done_traced(arx_renderer* r);
+arx_status fif_wait_scene(arx_renderer* r);
+arx_status fif_done_scene(arx_renderer* r);
 arx_status fif_wait_conv(arx_renderer* r);
+arx_status fif_done_conv(arx_renderer* r);
 arx_status fif_wait_reduced(arx_renderer* r);
 arx_status fif_done_reduced(arx_renderer* r);
-// Both frame sets' streams synchronised.
+// Every frame set's stream synchronised.
 arx_status sync_renderer(arx_renderer* r);
 // arx_convolute_device restricted to the file's one-second block pairs [pair_begin, pair_end)
-// (conv_run_pairs; the group's time-block shards).
+// (conv_run_pairs; the group's time-block shards); timed: recorded in the file-convolution ring.
 arx_status convolute_pairs(arx_renderer* r, const float* d_in, size_t n_frames, float* d_out_left, float* d_out_right,
-                           int64_t pair_begin, int64_t pair_end);
+                           int64_t pair_begin, int64_t pair_end, bool timed);
 // Whether the renderer's file convolution plan convolves a shard on its own (conv_plan_shards).
 bool conv_shards(arx_renderer* r);
+// Detach a streaming convolution from its renderer and release its device side (arx_destroy).
+void release_stream(arx_stream* s);
 }  // namespace arx
 
 // One renderer = one device (AudioRenderer, AudioRenderer.h:16-152).
@@ -117,21 +140,11 @@ struct arx_renderer {
     arx_config cfg;
     int32_t ir_len = 0;
     int cus = 256;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    // timing events: rings of (start, end) pairs around the last kTraceRing trace launches
-    // (arx_trace_times), file convolutions (arx_conv_times) and live / streaming convolutions
-    // (arx_live_times)
-    static constexpr int kTraceRing = 256;
-    hipEvent_t tev0[kTraceRing] = {}, tev1[kTraceRing] = {};
-    uint64_t trace_launches = 0;  // timed trace launches (the ring's index)
-    bool timing = true;           // arx_set_timing: record the per-launch events
-    hipEvent_t cev0[kTraceRing] = {}, cev1[kTraceRing] = {};
-    uint64_t conv_launches = 0;
-    hipEvent_t lev0[kTraceRing] = {}, lev1[kTraceRing] = {};
-    uint64_t live_launches = 0;
-    hipEvent_t aev0[kTraceRing] = {}, aev1[kTraceRing] = {};  // analyses (arx_analysis_times); made by the first one
-    uint64_t analysis_launches = 0;
+    hipStream_t stream = nullptr;  // the stream work is issued on now: the current set's, or arx_set_stream's
+    // timing events around the trace launches (arx_trace_times), file convolutions (arx_conv_times),
+    // live / streaming convolutions (arx_live_times) and analyses (arx_analysis_times; made at first use)
+    arx::EventRing trace_ring, conv_ring, live_ring, analysis_ring;
+    bool timing = true;  // arx_set_timing: record the per-launch events
 
     float emitter[3] = {0.f, 0.f, 0.f};
     float center[3] = {0.f, 0.f, 0.f};
@@ -178,16 +191,10 @@ struct arx_renderer {
     size_t tris_cap = 0;
     int32_t* d_gstack = nullptr;  // global traversal stack for trees deeper than the LDS stack
     size_t gstack_cap = 0;        // int32 entries
-    void* d_dirs = nullptr;       // direction pre-pass (float4 per ray of the largest trace call)
-    uint64_t dirs_cap = 0;
     bool force_global_stack = false;  // arx_debug_set_trace_path
     bool force_f32_nodes = false;
-    unsigned long long* d_hist = nullptr;  // 2*ir_len (own)
     unsigned long long* d_hist_ext = nullptr;  // caller-attached (arx_attach_histogram)
-    unsigned long long* hist() const { return d_hist_ext ? d_hist_ext : d_hist; }
-    float* d_ir = nullptr;                 // 2*ir_len: L then R
-    unsigned long long* d_counters = nullptr;
-    unsigned long long* h_counters = nullptr;  // pinned
+    unsigned long long* hist() const { return d_hist_ext ? d_hist_ext : cur().d_hist; }
     // The tree's off-grid flag (a receiver refit or re-quantization put a box outside the quantization
     // grid; its quantized copy then falls back to whole-axis boxes): one word per renderer, outside the
     // per-frame counters the direction pre-pass clears.  Each tree write (ensure_device_scene) runs with
@@ -213,14 +220,14 @@ struct arx_renderer {
     std::vector<arx_stream*> streams;  // live streaming convolutions of this renderer (arx_stream_create)
 
     // Frames in flight (arx_set_frames_in_flight, up to kMaxFrames): a frame's start
-    // (arx_clear_histogram) rotates the stream, histogram, IR, counters and direction buffer above
-    // with the sets in `alt`, so frame k + 1 traces on its own stream while frame k's trace finishes
+    // (arx_clear_histogram) takes the next of `sets` -- stream, histogram, IR, counters, direction
+    // buffer and analysis -- so frame k + 1 traces on its own stream while frame k's trace finishes
     // and its IR is convolved.  The frames wait for each other only where they share state: writes to
     // the shared scene / receiver buffers (and traces on the one global stack) for every other set's
     // last trace (ev_traced); each trace for the last scene writes (ev_scene), each use of the shared
     // convolution plans and of the caller's output buffers for the last convolution (ev_conv), a
     // group's all-reduce for the last all-reduce on the same communicator (ev_reduced).  `slot` names
-    // the set in the fields above; last_* the set that did the last such step (-1: none yet).
+    // the current set (cur()); last_* the set that did the last such step (-1: none yet).
     static constexpr int kMaxFrames = 3;
     // A frame's room-acoustic analysis (arx_analyze_ir): decay curves (3*ir_len), results (3) and the
     // kernels' scratch, allocated by the frame set's first analysis; queued: the frame that now owns
@@ -231,22 +238,23 @@ struct arx_renderer {
         void* d_scratch = nullptr;
         bool queued = false;
     };
-    Acoustics acou;             // the current set's
     bool auto_analyze = false;  // arx_set_auto_analyze
     int32_t scan_shape = 0;     // arx_debug_set_scan_shape (0: the product's)
     struct FrameSet {
         hipStream_t stream = nullptr;
-        unsigned long long* d_hist = nullptr;
-        float* d_ir = nullptr;
-        unsigned long long* d_counters = nullptr;
-        unsigned long long* h_counters = nullptr;
-        void* d_dirs = nullptr;
+        unsigned long long* d_hist = nullptr;      // 2*ir_len (own)
+        float* d_ir = nullptr;                     // 2*ir_len: L then R
+        unsigned long long* d_counters = nullptr;  // kCursor + 1 words
+        unsigned long long* h_counters = nullptr;  // pinned, kCounters words
+        void* d_dirs = nullptr;                    // direction pre-pass (float4 per ray of the largest trace call)
         uint64_t dirs_cap = 0;
         Acoustics acou;
     };
     int32_t fif = 1;
     int32_t slot = 0;
-    FrameSet alt[kMaxFrames - 1];
+    FrameSet sets[kMaxFrames];  // [0, fif) allocated
+    FrameSet& cur() { return sets[slot]; }
+    const FrameSet& cur() const { return sets[slot]; }
     hipEvent_t ev_traced[kMaxFrames] = {}, ev_conv[kMaxFrames] = {}, ev_reduced[kMaxFrames] = {},
                ev_scene[kMaxFrames] = {};
     int32_t last_conv = -1, last_reduced = -1, last_scene = -1;
@@ -257,3 +265,7 @@ struct arx_renderer {
     arx_stats stats;
 };
 
+namespace arx {
+// A frame set's analysis buffers released (with the set, or after a failed first allocation).
+void free_acoustics(arx_renderer::Acoustics& a);
+}  // namespace arx

@@ -96,6 +96,69 @@ def test_renderer_frames_in_flight_equal_one_at_a_time(conference, audio, trace_
     assert st1 == st2
 
 
+# frames in flight per frame: both growths (1 -> 3, twice) and both shrinks (3 -> 2, 2 -> 1)
+FIF_SCHEDULE = [1, 1, 3, 3, 3, 3, 2, 2, 2, 1, 3, 3]
+
+
+def run_schedule(conference, audio, change):
+    """Twelve frames cycling FRAMES, each render() (with its analysis) and a convolution into buffers of
+    its own, nothing synchronising between frames; change: set_frames_in_flight before every frame whose
+    number in FIF_SCHEDULE differs from the last one's.  Before those frames (changing or not) the
+    acoustics and counters of the frame just finished are read.  Returns the per-frame convolutions,
+    those reads, the last IR and the last frame's counters."""
+    r = AudioRenderer(RenderSettings(**S), scene=conference, receiver=receiver_local())
+    n = audio.size
+    x = DeviceBuffer.from_numpy(0, audio)
+    own = [(DeviceBuffer(0, 4 * n), DeviceBuffer(0, 4 * n)) for _ in FIF_SCHEDULE]
+    reads = []
+    try:
+        r.set_auto_analyze(True)
+        for k, (ol, orr) in enumerate(own):
+            lst, yaw, em, seed = FRAMES[k % len(FRAMES)]
+            if k > 0 and FIF_SCHEDULE[k] != FIF_SCHEDULE[k - 1]:
+                if change:
+                    r.set_frames_in_flight(FIF_SCHEDULE[k])
+                st = r.stats()
+                reads.append((r.acoustics("sum"), (st["queries"], st["receiver_hits"], st["misses"])))
+            r.setEmitterPosInOptix(em)
+            r.setSphereCenterInOptix(lst, yaw)
+            r.set_seed(seed)
+            r.render()
+            r.convolute_device(x.ptr, n, ol.ptr, orr.ptr)
+        ir = r.get_ir()  # synchronises the last frame
+        st = r.stats()
+        outs = [(ol.to_numpy(np.float32), orr.to_numpy(np.float32)) for ol, orr in own]
+        return outs, reads, ir, (st["queries"], st["receiver_hits"], st["misses"])
+    finally:
+        for b in [x] + [b for pair in own for b in pair]:
+            b.close()
+        r.close()
+
+
+def test_changing_frames_in_flight_between_frames(conference, audio):
+    """The number of frames in flight changes four times during one renderer's life: sets are
+    allocated, the current one is kept (its IR, counters and analysis still describe the last frame
+    right after the change) and sets are freed.  Everything equals the same frames on a renderer that
+    keeps one frame in flight."""
+    o1, reads1, ir1, st1 = run_schedule(conference, audio, change=False)
+    o2, reads2, ir2, st2 = run_schedule(conference, audio, change=True)
+    assert ir1[0].any() and st1[1] > 0
+    for k, (a, b) in enumerate(zip(o1, o2)):
+        assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1])), f"frame {k}"
+    # consecutive frames differ, so a stale set cannot pass for the current one
+    for k in range(len(o1) - 1):
+        assert not np.array_equal(o1[k][0], o1[k + 1][0]), f"frames {k}, {k + 1}"
+    assert len(reads1) == len(reads2) == 4
+    for i, ((a1, c1), (a2, c2)) in enumerate(zip(reads1, reads2)):
+        assert c1 == c2, f"counters after change {i}"
+        assert a1.keys() == a2.keys()
+        for key in a1:  # field for field; NaN (an invalid quantity) equals NaN
+            u, v = a1[key], a2[key]
+            assert u == v or (isinstance(u, float) and u != u and v != v), f"{key} after change {i}"
+    assert np.array_equal(bits(ir1[0]), bits(ir2[0])) and np.array_equal(bits(ir1[1]), bits(ir2[1]))
+    assert st1 == st2
+
+
 @pytest.mark.parametrize("frames", [2, 3])
 def test_ray_pool_launches_share_the_grid_in_flight(conference, audio, frames):
     """Launches large enough for the ray pool (C3's shape: 600K rays here) take half the CUs' wave

@@ -60,6 +60,28 @@ def test_renderer_timing_off_changes_only_the_rings(conference):
         r.close()
 
 
+def test_trace_ring_with_three_frames_in_flight(conference):
+    """The trace ring is the renderer's, not a frame set's: five timed renders over three sets leave
+    exactly their five times, oldest first, and untimed renders leave the ring alone."""
+    r = AudioRenderer(RenderSettings(**S), scene=conference, receiver=receiver_local())
+    try:
+        r.setEmitterPosInOptix(CONFERENCE_EMITTER)
+        r.setSphereCenterInOptix(CONFERENCE_LISTENER, 0.0)
+        r.set_frames_in_flight(3)
+        ms = [r.render() for _ in range(5)]  # each returns its own trace's time
+        times = r.trace_times(8)
+        assert len(times) == 5 and all(t > 0.0 for t in times)
+        assert list(times) == ms
+        assert r.stats()["trace_ms"] == times[-1]
+        r.set_timing(False)
+        for _ in range(2):
+            check(lib().arx_render(r.handle, None))
+        assert r.stats()["trace_ms"] == times[-1]
+        assert list(r.trace_times(8)) == ms
+    finally:
+        r.close()
+
+
 def test_group_timing_off(conference):
     g = RenderGroup(RenderSettings(**S), devices=[0], scene=conference, receiver=receiver_local())
     try:
