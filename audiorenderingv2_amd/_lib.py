@@ -145,6 +145,11 @@ SIGNATURES = {
     "arx_conv_describe": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t]),
     "arx_debug_ray_directions": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, _F, C.c_int]),
     "arx_debug_trace_counters": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_size_t]),
+    "arx_debug_set_ray_order": (C.c_int, [_P, C.c_int32]),
+    "arx_debug_ray_order_buffer": (C.c_int, [_P, _F, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_int32)]),
+    "arx_debug_ray_order_host": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "arx_debug_set_trace_path": (C.c_int, [_P, C.c_int]),
     "arx_debug_set_refit_pad": (C.c_int, [_P, C.c_float]),
     "arx_debug_check_tree_limits": (C.c_int, [C.c_uint64, C.c_uint64]),

@@ -160,6 +160,9 @@ void free_frame_set(arx_renderer::FrameSet& f) {
     hipFree(f.d_ir);
     hipFree(f.d_counters);
     hipFree(f.d_dirs);
+    hipFree(f.d_dirs_alt);
+    hipFree(f.d_cost);
+    hipFree(f.d_order_bins);
     if (f.h_counters) hipHostFree(f.h_counters);
     free_acoustics(f.acou);
     f = arx_renderer::FrameSet{};
@@ -336,9 +339,9 @@ arx_status arx_create(const arx_config* cfg, arx_renderer** out) {
         return cleanup(st);
     // the production trace kernels' register allocation, as the runtime sees it (arx_stats)
     for (int f = 0; f < 3; ++f)
-        for (int small = 0; small < 2; ++small)
-            if ((e = trace_kernel_occupancy(f, small != 0, &r->occ[f][small][0], &r->occ[f][small][1],
-                                            &r->occ[f][small][2])) != hipSuccess)
+        for (int inst = 0; inst < 3; ++inst)
+            if ((e = trace_kernel_occupancy(f, inst, &r->occ[f][inst][0], &r->occ[f][inst][1], &r->occ[f][inst][2])) !=
+                hipSuccess)
                 return cleanup(fail(ARX_ERR_HIP, "arx_create: trace kernel attributes: %s", hipGetErrorString(e)));
     r->stats.trace_vgprs = r->occ[kFmtQ16][0][0];
     r->stats.trace_waves_per_simd = r->occ[kFmtQ16][0][1];

@@ -458,6 +458,7 @@ arx_status arx::set_scene_image(arx_renderer* r, SceneRef img) {
     if (!validate_bvh_range(b.nodes.data(), 1, b.nodes.size(), 1 + b.nodes.size(), b.tris.size(), &why))
         return fail(ARX_ERR_INTERNAL, "BVH validation failed (scene): %s", why);
     r->scene_img = std::move(img);
+    ++r->scene_gen;
     r->scene_dirty = true;
     r->recv_model_dirty = true;  // receiver ids and offsets follow the scene
     return ARX_OK;
@@ -519,14 +520,15 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
         if (clear) ARX_HIP(launch_clear(r->hist(), 2 * (uint64_t)r->ir_len, f.d_counters, (int)kCounters, r->stream));
         return ARX_OK;
     }
-    if (ray_end - ray_begin > f.dirs_cap) {  // direction pre-pass buffer
+    const uint64_t n_launch = ray_end - ray_begin;
+    if (n_launch > f.dirs_cap) {  // direction pre-pass buffer; what the old one held is forgotten
         if (f.d_dirs) ARX_HIP(hipFree(f.d_dirs));
         f.d_dirs = nullptr;
         f.dirs_cap = 0;
-        ARX_HIP(hipMalloc(&f.d_dirs, (ray_end - ray_begin) * 16));
-        f.dirs_cap = ray_end - ray_begin;
+        f.dirs_valid = f.dirs_sorted = false;
+        ARX_HIP(hipMalloc(&f.d_dirs, n_launch * 16));
+        f.dirs_cap = n_launch;
     }
-    a.dirs = f.d_dirs;
     const bool gstack = r->force_global_stack || a.bvh_depth + 1 > kLdsStack;
     // CW4: up to three pushes per level; the rows beyond the LDS rows overflow into a global column
     const size_t w4_rows = (size_t)std::max(1, 3 * r->depth4 + 3 - kLdsStack);
@@ -562,10 +564,55 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     const int fmt = a.wbuf ? kFmtW4 : (a.qnodes ? kFmtQ16 : kFmtF32);
     // the instance launch_trace takes (ray pool or small launch): the profile guard reads these
     const int small = trace_uses_small_block(a, r->cus, r->force_global_stack) ? 1 : 0;
+    // The direction buffer across launches (arx_debug_set_ray_order, include/arx.h).  Kept while seed
+    // and ray range stay (every launch kind); for launches that take the pool on the 16-bit LDS-stack
+    // instance, the pool's slots ordered longest first: the first launch of a key runs the measuring
+    // instance on directions in ray order and the sort follows it on the same stream into the set's
+    // second buffer; the launches after it run the product instance on that buffer as long as the key
+    // holds.  Per frame set: its own stream and buffers, nothing new crosses streams.
+    // (a caller's other stream, arx_set_stream, is not ordered after the launch that wrote them: re-made)
+    const bool kept = r->ray_order != 2 && f.dirs_valid && f.dirs_stream == r->stream && f.dirs_seed == c.seed &&
+                      f.dirs_begin == ray_begin && f.dirs_count == n_launch;
+    const bool ordered = r->ray_order == 1 && trace_can_measure(a, r->cus, r->force_global_stack);
+    OrderKey key;
+    std::memset(&key, 0, sizeof(key));
+    if (ordered) {
+        key.scene_gen = r->scene_gen;
+        key.tree_hash = r->stats.tree_hash;
+        key.seed = c.seed;
+        key.ray_begin = ray_begin;
+        key.ray_end = ray_end;
+        for (int k = 0; k < 3; ++k) key.emitter[k] = r->emitter[k];
+        key.e0 = a.e0;
+        key.energy_thres = a.energy_thres;
+        key.hrtf = a.hrtf;
+        key.dist_limit = a.dist_limit;
+        key.max_bounces = a.max_bounces;
+        key.dyn_share = trace_pool_share();
+        key.is_mono = a.is_mono;
+        key.instance = fmt;
+    }
+    const bool use_sorted = ordered && kept && f.dirs_sorted && std::memcmp(&key, &f.order_key, sizeof(key)) == 0;
+    const bool measure = ordered && !use_sorted;
+    const bool fill_dirs = !use_sorted && !(kept && !f.dirs_sorted);
+    if (measure && f.order_cap != f.dirs_cap) {  // the two buffers swap: always the same size
+        hipFree(f.d_dirs_alt);
+        hipFree(f.d_cost);
+        f.d_dirs_alt = nullptr;
+        f.d_cost = nullptr;
+        f.order_cap = 0;
+        ARX_HIP(hipMalloc(&f.d_dirs_alt, f.dirs_cap * 16));
+        ARX_HIP(hipMalloc(&f.d_cost, f.dirs_cap * sizeof(unsigned short)));
+        if (!f.d_order_bins) ARX_HIP(hipMalloc(&f.d_order_bins, order_bins_bytes()));
+        f.order_cap = f.dirs_cap;
+    }
+    a.dirs = f.d_dirs;
+    a.cost = measure ? f.d_cost : nullptr;
+    const int inst = measure ? kInstMeasure : (small ? kInstSmall : kInstPool);
     r->stats.trace_format = fmt;
-    r->stats.trace_vgprs = r->occ[fmt][small][0];
-    r->stats.trace_waves_per_simd = r->occ[fmt][small][1];
-    r->stats.trace_waves_target = r->occ[fmt][small][2];
+    r->stats.trace_vgprs = r->occ[fmt][inst][0];
+    r->stats.trace_waves_per_simd = r->occ[fmt][inst][1];
+    r->stats.trace_waves_target = r->occ[fmt][inst][2];
     if (timed && (st = r->trace_ring.begin(r->stream)) != ARX_OK) return st;
     // Frames in flight: a ray-pool launch is sized for half the CUs' wave slots, so the next frame's
     // launch runs beside it for its whole length instead of only in its tail.  A launch of 1M rays
@@ -582,7 +629,20 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     const bool shared_grid = r->fif >= 2 && !small && !gstack && !a.wbuf;
     const int grid_cus = shared_grid ? std::max(1, r->cus * ARX_SHARED_GRID_PCT / 100) : r->cus;
     r->stats.trace_grid_cus = grid_cus;
-    ARX_HIP(launch_trace(a, grid_cus, r->stream, r->force_global_stack));
+    f.dirs_valid = false;  // until the launches below are issued
+    ARX_HIP(launch_trace(a, grid_cus, r->stream, r->force_global_stack, fill_dirs));
+    f.dirs_stream = r->stream;
+    f.dirs_seed = c.seed;
+    f.dirs_begin = ray_begin;
+    f.dirs_count = n_launch;
+    f.dirs_sorted = use_sorted;
+    if (measure) {  // inside the launch's timing window: a cost this frame pays
+        ARX_HIP(launch_order_pool(f.d_dirs, f.d_dirs_alt, f.d_cost, f.d_order_bins, n_launch, r->stream));
+        std::swap(f.d_dirs, f.d_dirs_alt);
+        f.order_key = key;
+        f.dirs_sorted = true;
+    }
+    f.dirs_valid = true;
     if (timed && (st = r->trace_ring.end(r->stream)) != ARX_OK) return st;
     return fif_done_traced(r);
 }
@@ -787,6 +847,35 @@ arx_status arx_debug_set_trace_path(arx_renderer* r, int path) {
         r->recv_model_dirty = true;
     }
     r->use_w4 = w4;
+    return ARX_OK;
+}
+
+arx_status arx_debug_set_ray_order(arx_renderer* r, int32_t mode) {
+    if (!r || mode < 0 || mode > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "ray order: 0, 1 or 2");
+    r->ray_order = mode;
+    return ARX_OK;
+}
+
+arx_status arx_debug_ray_order_buffer(arx_renderer* r, float* h_out_xyzw, uint64_t count, uint64_t* first_ray,
+                                      uint64_t* n_static, int32_t* sorted) {
+    if (!r || (count > 0 && !h_out_xyzw)) return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
+    const arx_renderer::FrameSet& f = r->cur();
+    if (!f.dirs_valid) return fail(ARX_ERR_NOT_READY, "no trace on this frame set yet");
+    if (count > f.dirs_count) return fail(ARX_ERR_INVALID_ARGUMENT, "the buffer holds %llu rays", (unsigned long long)f.dirs_count);
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    if (count > 0) ARX_HIP(hipMemcpy(h_out_xyzw, f.d_dirs, count * 16, hipMemcpyDeviceToHost));
+    if (first_ray) *first_ray = f.dirs_begin;
+    if (n_static) *n_static = f.dirs_sorted ? pool_static_rays(f.dirs_count, trace_pool_share()) : f.dirs_count;
+    if (sorted) *sorted = f.dirs_sorted ? 1 : 0;
+    return ARX_OK;
+}
+
+arx_status arx_debug_ray_order_host(uint64_t n, uint32_t dyn_share, uint32_t steps, uint64_t* n_static, uint32_t* cost16,
+                                    uint32_t* build_share) {
+    if (n_static) *n_static = pool_static_rays(n, dyn_share);
+    if (cost16) *cost16 = ray_cost16(steps);
+    if (build_share) *build_share = trace_pool_share();
     return ARX_OK;
 }
 

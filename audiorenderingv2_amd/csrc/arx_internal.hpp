@@ -85,9 +85,22 @@ SceneRef deserialize_scene(const uint8_t* p, size_t n, const char** why);
 
 }  // namespace arx
 
+#ifndef ARX_RAY_ORDER_DEFAULT
+#define ARX_RAY_ORDER_DEFAULT 1  // design experiments only (build.py --exp): arx_debug_set_ray_order's default
+#endif
 struct arx_renderer;
 struct arx_stream;
 namespace arx {
+// Everything that changes a ray's path or length, so the per-ray costs one launch measured order the
+// pool of the next: a frame set keeps its sorted direction buffer while this stays the same.  The
+// listener's position and yaw are deliberately not in it (a few percent of the rays touch the receiver).
+struct OrderKey {
+    uint64_t scene_gen, tree_hash, seed, ray_begin, ray_end;
+    float emitter[3];
+    float e0, energy_thres, hrtf, dist_limit;
+    uint32_t max_bounces, dyn_share;
+    int32_t is_mono, instance;
+};
 // A ring of (start, end) event pairs around the last kTraceRing timed launches of one kind.  A launch
 // that is not timed records nothing and does not advance the ring.
 constexpr int kTraceRing = 256;
@@ -181,7 +194,9 @@ struct arx_renderer {
     int32_t* d_recv_w4_tris = nullptr;
     bool use_w4 = false;           // arx_debug_set_trace_path bit 3: the CW4 tree
     int32_t depth4 = 0;            // CW4 levels (top node included): bounds the stack (3 per level)
-    int32_t occ[3][2][3] = {};     // per node format and instance (0 pool, 1 small launches): VGPRs, waves admitted, waves targeted
+    int32_t occ[3][3][3] = {};     // per node format and instance (kInstPool, kInstSmall, kInstMeasure): VGPRs, waves admitted, waves targeted
+    int32_t ray_order = ARX_RAY_ORDER_DEFAULT;  // arx_debug_set_ray_order: 0 identity, directions kept; 1 longest-first pool; 2 directions re-made per launch
+    uint64_t scene_gen = 0;        // scenes installed (set_scene_image): part of a frame set's OrderKey
     arx::QGrid qgrid{};
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)
@@ -248,6 +263,20 @@ struct arx_renderer {
         unsigned long long* h_counters = nullptr;  // pinned, kCounters words
         void* d_dirs = nullptr;                    // direction pre-pass (float4 per ray of the largest trace call)
         uint64_t dirs_cap = 0;
+        // What d_dirs holds, so a launch of the same seed and range skips the pre-pass's directions
+        // (forgotten when the buffer is reallocated): the rays [dirs_begin, dirs_begin + dirs_count)
+        // of dirs_seed, in ray order or (dirs_sorted) with the pool's slots ordered for order_key,
+        // written on dirs_stream.
+        bool dirs_valid = false, dirs_sorted = false;
+        hipStream_t dirs_stream = nullptr;
+        uint64_t dirs_seed = 0, dirs_begin = 0, dirs_count = 0;
+        arx::OrderKey order_key{};
+        // the longest-first pool (made by the set's first measuring launch): the buffer the sort
+        // writes (swapped with d_dirs after it), per-slot costs, the sort's bins
+        void* d_dirs_alt = nullptr;
+        unsigned short* d_cost = nullptr;
+        uint32_t* d_order_bins = nullptr;
+        uint64_t order_cap = 0;                    // slots of d_dirs_alt and d_cost
         Acoustics acou;
     };
     int32_t fif = 1;

@@ -14,7 +14,21 @@ namespace arx {
 // [a.ray_begin, a.ray_end); cus = compute units of the device (persistent grid size).
 // Quantized nodes when a.qnodes is set, else the f32 coded nodes; the global-memory stack when
 // the tree is deeper than the LDS stack or force_global_stack (a parity hook).
-hipError_t launch_trace(const TraceArgs& a, int cus, hipStream_t s, bool force_global_stack = false);
+// fill_dirs false: a.dirs already holds this launch's directions (kept from an earlier launch of the same
+// seed and ray range, in any order of the pool's slots); the pre-pass then only clears and resets
+// the pool cursor.  With a.cost set, a launch that takes the pool on the 16-bit LDS-stack instance
+// (trace_can_measure) runs its measuring instance; every other launch ignores it.
+hipError_t launch_trace(const TraceArgs& a, int cus, hipStream_t s, bool force_global_stack = false,
+                        bool fill_dirs = true);
+bool trace_can_measure(const TraceArgs& a, int cus, bool force_global_stack);
+// The pool's share of a launch's rays in this build, in 1/256 (pool_static_rays' dyn_share).
+uint32_t trace_pool_share();
+// Longest-first pool: dirs_out = dirs_in with the pool's slots [pool_static_rays(n, trace_pool_share()), n)
+// permuted by descending cost (the measuring launch's a.cost) and the static slots copied; bins:
+// order_bins_bytes() of device scratch.  All on s, nothing waits on the host.
+hipError_t launch_order_pool(const void* dirs_in, void* dirs_out, const unsigned short* cost, uint32_t* bins, uint64_t n,
+                             hipStream_t s);
+size_t order_bins_bytes();
 // Lanes of the largest persistent trace grid (columns of the global traversal stack).
 inline uint64_t trace_max_lanes(int cus) { return (uint64_t)(cus > 0 ? cus : 256) * 2048ull; }
 // i64 histogram -> f32 IR (+ mono merge); unit = e0 * 2^-frac_bits.
@@ -29,7 +43,8 @@ hipError_t launch_ray_directions(uint64_t seed, uint64_t first, uint64_t count, 
 // waves per SIMD it admits, and the waves per SIMD the persistent grid is sized for.
 // Register allocation of the LDS-stack trace instance of node format fmt, the large-launch (ray pool)
 // or the small-launch one (small), and which of the two launch_trace takes for these arguments.
-hipError_t trace_kernel_occupancy(int fmt, bool small, int* vgprs, int* waves_admitted, int* waves_target);
+constexpr int kInstPool = 0, kInstSmall = 1, kInstMeasure = 2;  // the pool's measuring instance (16-bit nodes only)
+hipError_t trace_kernel_occupancy(int fmt, int instance, int* vgprs, int* waves_admitted, int* waves_target);
 bool trace_uses_small_block(const TraceArgs& a, int cus, bool force_global_stack);
 // identity of the trace kernel in this build (build.py trace_source_id; arx_trace_kernel_id)
 uint64_t trace_kernel_source_id();

@@ -148,7 +148,24 @@ struct TraceArgs {
     uint32_t dyn_chunk;          // rays per pool atomic
     uint64_t clear_bins;         // > 0: the direction pre-pass also zeroes hist[0, clear_bins) ...
     int32_t clear_counters;      // ... and counters[0, clear_counters) (render(): no separate clear launch)
+    unsigned short* cost;        // per direction-buffer slot, the steps of its ray (the measuring instance only; null otherwise)
 };
+
+// Rays of a launch of n dealt out statically (slots [0, n_static) of the direction buffer, one range
+// per wave); the other n * dyn_share / 256 form the pool (trace_kernel).  The kernel and the host's
+// ordering of the pool's slots (launch_order_pool) both take it from here.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define ARX_HOST_DEVICE __host__ __device__
+#else
+#define ARX_HOST_DEVICE
+#endif
+ARX_HOST_DEVICE inline uint64_t pool_static_rays(uint64_t n, uint32_t dyn_share) {
+    return n - ((n * (uint64_t)dyn_share) >> 8);
+}
+// A ray's step count as the measuring instance stores it: saturated to 16 bits, never wrapped.
+ARX_HOST_DEVICE inline unsigned short ray_cost16(uint32_t steps) {
+    return (unsigned short)(steps > 65535u ? 65535u : steps);
+}
 // Node formats of the trace kernel (arx_stats::trace_format)
 constexpr int kFmtF32 = 0, kFmtQ16 = 1, kFmtW4 = 2;
 // Per-wave record of a profiling build (ARX_TRACE_PROF=1, arx_debug_trace_profile): u64 words

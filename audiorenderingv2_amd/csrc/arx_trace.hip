@@ -16,8 +16,9 @@
 // Arithmetic is IEEE f32 with no contraction (built -ffp-contract=off) so that every ray follows
 // bit for bit the path computed by the CPU oracle (oracle/arx_oracle.c).
 //
-// This file holds only the production kernel (one template, four instances: quantized or f32
-// nodes x LDS or global stack).  The round-1 design experiments (wide trees, octant copies,
+// This file holds only the production kernel (one template; instances: quantized, f32 or CW4 nodes x
+// LDS or global stack x ray-pool or small launch, and the pool's measuring instance, which feeds the
+// longest-first order of the pool's direction slots: see launch_order_pool).  The round-1 design experiments (wide trees, octant copies,
 // cooperative fetch, LDS node caches, ray pools, phased launches) are in
 // the git history at commit 62a5de6 (audiorenderingv2_amd/csrc/arx_trace.hip).
 #include <hip/hip_runtime.h>
@@ -770,7 +771,14 @@ constexpr int kDynShare = ARX_TRACE_DYN_SHARE, kDynChunk = ARX_TRACE_DYN_CHUNK, 
 // LEAN (the small-launch instance): no per-lane "traversing" flag -- a lane's query is done when its
 // node is -1 -- so the inner loop counts the lanes waiting for shading from wave masks on the SALU
 // (C2 0.366 -> 0.350 ms; the pool instance measured +1 % with it, profiles/r05/ab_loop.txt).
-template <int BLOCK, int THRESH, int LEAF_THRESH, int MINW, int NSTEPS, int FMT, bool GSTACK, bool LEAN = false>
+// MEASURE (the measuring instance of the pool kernel, 16-bit nodes and LDS stack only): each lane counts
+// the node steps and leaf steps of its current ray and, when it retires the ray, stores the count
+// (ray_cost16; the largest count for a ray that ended on the receiver) into a.cost[slot], slot being
+// the direction-buffer index the lane took at refill.  The
+// launcher orders the pool's slots by that cost for the following launches (launch_order_pool).  Same
+// rays, same arithmetic, same counters as the product instance, whose code this parameter leaves alone.
+template <int BLOCK, int THRESH, int LEAF_THRESH, int MINW, int NSTEPS, int FMT, bool GSTACK, bool LEAN = false,
+          bool MEASURE = false>
 __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
     constexpr bool Q16 = FMT == kFmtQ16;
     constexpr bool W4 = FMT == kFmtW4;
@@ -824,9 +832,9 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
     // pool handed out in chunks of kDynChunk rays, one atomic per chunk, to waves whose static range
     // has run out -- equal work per wave still leaves waves finishing at different times (their
     // SIMD, CU and XCD neighbours differ), and the pool lets the fast ones finish the launch.
-    const uint64_t n_dyn = (n * (uint64_t)a.dyn_share) >> 8;
     const uint32_t dyn_chunk = a.dyn_chunk;
-    const uint64_t n_static = n - n_dyn;
+    const uint64_t n_static = pool_static_rays(n, a.dyn_share);
+    const uint64_t n_dyn = n - n_static;
     uint64_t w_next = n_static * wave_id / n_waves;
     uint64_t w_end = n_static * (wave_id + 1) / n_waves;
     uint32_t n_q = 0, n_rx = 0, n_miss = 0;
@@ -860,6 +868,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
     t.node = -1;
     t.sp = 0;
     float oix = 0.f, oiy = 0.f, oiz = 0.f;
+    uint32_t m_slot = 0u, m_cost = 0u;  // MEASURE: the current ray's buffer slot and its steps so far
     while (true) {
 #if ARX_TRACE_PROF
         ++pf[10];
@@ -872,8 +881,16 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
         }
 #endif
         if (active && (LEAN ? t.node == -1 : !trav)) {  // the query is done: shade it
+            const uint32_t rx_before = n_rx;
             shade(a, tbase, s, r, t.best, n_rx, n_miss);
-            if (!wants_query(a, s)) active = false;
+            if (!wants_query(a, s)) {
+                active = false;
+                // the ray retires.  One the receiver ended says nothing about its length once the
+                // listener has moved (the order outlives listener moves): it counts as the longest,
+                // so it starts first -- ranked by its short count it would start last and, running its
+                // full length from the listener's next position, be the launch's tail again
+                if constexpr (MEASURE) a.cost[m_slot] = n_rx != rx_before ? (unsigned short)65535u : ray_cost16(m_cost);
+            }
         }
         const unsigned long long need = __ballot(!active);
 #if ARX_TRACE_PROF
@@ -903,6 +920,11 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
                 if (i < w_end) {
                     ray_init(a, s, a.ray_begin + i);
                     active = wants_query(a, s);
+                    if constexpr (MEASURE) {
+                        m_slot = (uint32_t)i;  // i < n <= 2^31 - 1 rays
+                        m_cost = 0u;
+                        if (!active) a.cost[i] = 0;  // a ray that never queries
+                    }
                 }
             }
             if (w_next >= w_end && n_dyn == 0) exhausted = true;
@@ -978,6 +1000,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
 #if ARX_TRACE_COUNT
                         ++n_steps;
 #endif
+                        if constexpr (MEASURE) ++m_cost;
                         if constexpr (W4) node_step_w4(r, oix, oiy, oiz, t, stk, nrs);
                         else node_step<FMT, Stack, !LEAN>(r, oix, oiy, oiz, t, stk, nrs, ncache, qrs);
                     }
@@ -990,6 +1013,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
 #if ARX_TRACE_COUNT
                 if (t.node <= -2) n_tris += (uint32_t)((~t.node) & (W4 ? 3 : 15));
 #endif
+                if constexpr (MEASURE) m_cost += t.node <= -2 ? 1u : 0u;
                 leaf_step<FMT>(trs, r, t, stk);
             }
         }
@@ -1062,6 +1086,95 @@ __global__ void dirs_kernel(uint64_t seed, uint64_t first, uint64_t count, float
     out[i] = make_float4(d.x, d.y, d.z, 0.0f);
 }
 
+// ------------------------------------------------- longest-first ray pool ---
+// The pool hands out direction-buffer slots [n_static, n) in order, so the order of those slots is
+// the order rays start in; the rays that start last set the launch's tail.  After a measuring launch
+// (trace_kernel<MEASURE>) a counting sort by descending cost rewrites the pool's slots into the frame
+// set's second buffer: a histogram over cost >> kOrderShift (LDS per block, then global), a one-block
+// scan, and a scatter that gives each slot a place in its bin (the order inside a bin is free: the
+// histogram and the counters do not depend on the order rays run in).  Slots below n_static are
+// copied as they are.
+constexpr int kOrderShift = 3;
+constexpr int kOrderBins = 65536 >> kOrderShift;  // 8192 bins of 8 steps (a C3 ray takes 566 +- 94)
+constexpr int kOrderTile = 8192;                  // slots per block of the histogram pass
+constexpr int kOrderScanBlock = 1024;
+static_assert(kOrderBins % kOrderScanBlock == 0, "the scan gives each lane a whole number of bins");
+__device__ __forceinline__ uint32_t order_bin(unsigned short cost) {  // the costliest rays in bin 0
+    return (uint32_t)(kOrderBins - 1) - ((uint32_t)cost >> kOrderShift);
+}
+
+__global__ __launch_bounds__(256) void order_hist_kernel(const unsigned short* __restrict__ cost, uint64_t n_static,
+                                                         uint64_t n, uint32_t* __restrict__ bins) {
+    __shared__ uint32_t h[kOrderBins];
+    for (int b = threadIdx.x; b < kOrderBins; b += 256) h[b] = 0u;
+    __syncthreads();
+    const uint64_t base = n_static + (uint64_t)blockIdx.x * kOrderTile;
+    const uint64_t end = base + kOrderTile < n ? base + kOrderTile : n;
+    for (uint64_t i = base + threadIdx.x; i < end; i += 256) atomicAdd(&h[order_bin(cost[i])], 1u);
+    __syncthreads();
+    for (int b = threadIdx.x; b < kOrderBins; b += 256)
+        if (h[b]) atomicAdd(&bins[b], h[b]);
+}
+
+// bins[b] = the number of pool slots in bins [0, b): one block, kOrderBins / kOrderScanBlock bins per lane
+__global__ __launch_bounds__(kOrderScanBlock) void order_scan_kernel(uint32_t* __restrict__ bins) {
+    constexpr int per = kOrderBins / kOrderScanBlock;
+    __shared__ uint32_t part[kOrderScanBlock];
+    const int t = threadIdx.x;
+    uint32_t v[per], sum = 0u;
+#pragma unroll
+    for (int k = 0; k < per; ++k) {
+        v[k] = bins[t * per + k];
+        sum += v[k];
+    }
+    part[t] = sum;
+    __syncthreads();
+    for (int off = 1; off < kOrderScanBlock; off <<= 1) {
+        const uint32_t x = t >= off ? part[t - off] : 0u;
+        __syncthreads();
+        part[t] += x;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - sum;
+#pragma unroll
+    for (int k = 0; k < per; ++k) {
+        bins[t * per + k] = run;
+        run += v[k];
+    }
+}
+
+// One tile of kOrderTile pool slots per block, the histogram pass's tiles.  A slot's rank among its
+// tile's slots of the same bin comes from an LDS atomic; one global atomic per (tile, occupied bin)
+// then reserves the tile's run in that bin, instead of one per slot on a few dozen hot words (which
+// took 0.73 ms at C3; the three passes now take 12 + 5 + 20 us).  The bins hold exactly the n - n_static
+// pool slots the histogram pass counted from the same cost buffer, so every destination is in
+// [n_static, n).
+__global__ __launch_bounds__(256) void order_scatter_kernel(const float4* __restrict__ in,
+                                                            const unsigned short* __restrict__ cost, uint64_t n_static,
+                                                            uint64_t n, uint32_t* __restrict__ bins,
+                                                            float4* __restrict__ out) {
+    constexpr int per = kOrderTile / 256;
+    __shared__ uint32_t h[kOrderBins];
+    for (int b = threadIdx.x; b < kOrderBins; b += 256) h[b] = 0u;
+    __syncthreads();
+    const uint64_t base = n_static + (uint64_t)blockIdx.x * kOrderTile;
+    uint32_t rank[per];
+#pragma unroll
+    for (int k = 0; k < per; ++k) {
+        const uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
+        rank[k] = i < n ? atomicAdd(&h[order_bin(cost[i])], 1u) : 0u;
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < kOrderBins; b += 256)
+        if (h[b]) h[b] = atomicAdd(&bins[b], h[b]);  // the tile's first place in bin b
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < per; ++k) {
+        const uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
+        if (i < n) out[n_static + h[order_bin(cost[i])] + rank[k]] = in[i];
+    }
+}
+
 
 __global__ void ray_dir_kernel(uint64_t seed, uint64_t first, uint64_t count, float* out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1126,7 +1239,7 @@ bool uses_pool(const TraceArgs& args, int cus) {
 }
 
 template <int FMT, bool GSTACK>
-hipError_t launch(const TraceArgs& args, int cus, hipStream_t s) {
+hipError_t launch(const TraceArgs& args, int cus, hipStream_t s, bool fill_dirs) {
     const uint64_t n_rays = args.ray_end - args.ray_begin;
 #ifdef ARX_TRACE_DYN_LDS
     static const size_t dyn_lds = ARX_TRACE_DYN_LDS;  // design experiments only
@@ -1138,10 +1251,21 @@ hipError_t launch(const TraceArgs& args, int cus, hipStream_t s) {
     const bool dyn = uses_pool<FMT, GSTACK>(args, cus);
     a2.dyn_share = dyn ? (uint32_t)kDynShare : 0u;
     a2.dyn_chunk = (uint32_t)kDynChunk;
-    const uint64_t pre = std::max<uint64_t>(n_rays, args.clear_bins);
+    // the pre-pass: with the buffer's directions kept from an earlier launch (fill_dirs false) only the
+    // fused clear and the pool-cursor reset, which lives in its lane 0 -- so at least one block
+    const uint64_t n_fill = fill_dirs ? n_rays : 0;
+    const uint64_t pre = std::max<uint64_t>(std::max<uint64_t>(n_fill, args.clear_bins), 1);
     hipLaunchKernelGGL(dirs_kernel, dim3((unsigned)((pre + 255) / 256)), dim3(256), 0, s, args.seed, args.ray_begin,
-                       n_rays, reinterpret_cast<float4*>(const_cast<void*>(args.dirs)), args.cursor, args.hist,
+                       n_fill, reinterpret_cast<float4*>(const_cast<void*>(args.dirs)), args.cursor, args.hist,
                        args.clear_bins, args.counters, args.clear_counters);
+    if constexpr (FMT == kFmtQ16 && !GSTACK) {
+        if (dyn && args.cost) {  // the measuring instance of the pool kernel
+            hipLaunchKernelGGL((trace_kernel<kBlock, kThresh, kLeafThresh, kWaves, kSteps, FMT, GSTACK, false, true>),
+                               dim3(grid), dim3(kBlock), dyn_lds, s, a2);
+            return hipGetLastError();
+        }
+    }
+    a2.cost = nullptr;
     if (kSmallBlock > 0 && !dyn) {
         // Small launches (about a ray per lane: C2, one 8-GPU rank's C5 shard) in 4-wave blocks,
         // one wave per SIMD each: 0.465 -> 0.44 ms at C2
@@ -1158,18 +1282,18 @@ hipError_t launch(const TraceArgs& args, int cus, hipStream_t s) {
 
 }  // namespace
 
-hipError_t launch_trace(const TraceArgs& a, int cus, hipStream_t s, bool force_global_stack) {
+hipError_t launch_trace(const TraceArgs& a, int cus, hipStream_t s, bool force_global_stack, bool fill_dirs) {
     if (a.ray_end <= a.ray_begin) return hipSuccess;
     (void)hipGetLastError();  // report this launch's error, not a stale one of an earlier runtime call
     if (!a.dirs || !a.cnodes || !a.tris || !a.hist || !a.counters || !a.cursor) return hipErrorInvalidValue;
     if (a.wbuf) {  // CW4: LDS rows + a global overflow column per lane (W4Stack)
         if (!a.gstack || a.gstack_lanes < (uint64_t)kBlock) return hipErrorInvalidValue;
-        return launch<kFmtW4, false>(a, cus, s);
+        return launch<kFmtW4, false>(a, cus, s, fill_dirs);
     }
     const bool gstack = force_global_stack || a.bvh_depth + 1 > kLdsStack;
     if (gstack && (!a.gstack || a.gstack_lanes < (uint64_t)kBlock)) return hipErrorInvalidValue;
-    if (a.qnodes) return gstack ? launch<kFmtQ16, true>(a, cus, s) : launch<kFmtQ16, false>(a, cus, s);
-    return gstack ? launch<kFmtF32, true>(a, cus, s) : launch<kFmtF32, false>(a, cus, s);
+    if (a.qnodes) return gstack ? launch<kFmtQ16, true>(a, cus, s, fill_dirs) : launch<kFmtQ16, false>(a, cus, s, fill_dirs);
+    return gstack ? launch<kFmtF32, true>(a, cus, s, fill_dirs) : launch<kFmtF32, false>(a, cus, s, fill_dirs);
 }
 
 #ifndef ARX_TRACE_SRC_ID
@@ -1185,6 +1309,34 @@ bool trace_uses_small_block(const TraceArgs& a, int cus, bool force_global_stack
     return gstack ? !uses_pool<kFmtF32, true>(a, cus) : !uses_pool<kFmtF32, false>(a, cus);
 }
 
+bool trace_can_measure(const TraceArgs& a, int cus, bool force_global_stack) {
+    if (a.ray_end <= a.ray_begin || a.wbuf || !a.qnodes) return false;
+    if (force_global_stack || a.bvh_depth + 1 > kLdsStack) return false;
+    return uses_pool<kFmtQ16, false>(a, cus);
+}
+
+uint32_t trace_pool_share() { return (uint32_t)kDynShare; }
+
+hipError_t launch_order_pool(const void* dirs_in, void* dirs_out, const unsigned short* cost, uint32_t* bins, uint64_t n,
+                             hipStream_t s) {
+    (void)hipGetLastError();
+    if (!dirs_in || !dirs_out || !cost || !bins) return hipErrorInvalidValue;
+    const uint64_t n_static = pool_static_rays(n, (uint32_t)kDynShare);
+    if (n_static >= n) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(bins, 0, kOrderBins * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    const uint64_t tiles = (n - n_static + kOrderTile - 1) / kOrderTile;
+    hipLaunchKernelGGL(order_hist_kernel, dim3((unsigned)tiles), dim3(256), 0, s, cost, n_static, n, bins);
+    hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(kOrderScanBlock), 0, s, bins);
+    hipLaunchKernelGGL(order_scatter_kernel, dim3((unsigned)tiles), dim3(256), 0, s,
+                       reinterpret_cast<const float4*>(dirs_in), cost, n_static, n, bins,
+                       reinterpret_cast<float4*>(dirs_out));
+    const hipError_t e2 = hipGetLastError();
+    if (e2 != hipSuccess || n_static == 0) return e2;
+    return hipMemcpyAsync(dirs_out, dirs_in, n_static * 16, hipMemcpyDeviceToDevice, s);  // the static ranges as they are
+}
+size_t order_bins_bytes() { return kOrderBins * sizeof(uint32_t); }
+
 namespace {
 template <int B, int L, int S, bool LEAN>
 const void* lds_stack_instance(int fmt) {
@@ -1195,11 +1347,15 @@ const void* lds_stack_instance(int fmt) {
 }
 }  // namespace
 
-hipError_t trace_kernel_occupancy(int fmt, bool small, int* vgprs, int* waves_admitted, int* waves_target) {
+hipError_t trace_kernel_occupancy(int fmt, int instance, int* vgprs, int* waves_admitted, int* waves_target) {
     hipFuncAttributes fa;
     constexpr int SB = kSmallBlock > 0 ? kSmallBlock : kBlock;
+    const bool small = instance == kInstSmall;
     const void* k = small ? lds_stack_instance<SB, kSmallLeaf, kSmallSteps, true>(fmt)
                           : lds_stack_instance<kBlock, kLeafThresh, kSteps, false>(fmt);
+    if (instance == kInstMeasure && fmt == kFmtQ16)  // the other formats have no measuring instance: their pool one
+        k = reinterpret_cast<const void*>(
+            trace_kernel<kBlock, kThresh, kLeafThresh, kWaves, kSteps, kFmtQ16, false, false, true>);
     const hipError_t e = hipFuncGetAttributes(&fa, k);
     if (e != hipSuccess) return e;
     // gfx950: 512 VGPRs per SIMD lane slot, allocated in granules of 8

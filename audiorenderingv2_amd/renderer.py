@@ -217,6 +217,21 @@ class AudioRenderer:
         global-memory traversal stack; 0 = automatic."""
         check(lib().arx_debug_set_trace_path(self.handle, int(path)))
 
+    def set_ray_order(self, mode: int) -> None:
+        """arx_debug_set_ray_order: 0 directions kept in ray order, 1 (default) the ray pool's slots
+        longest ray first, 2 directions re-made by every launch."""
+        check(lib().arx_debug_set_ray_order(self.handle, int(mode)))
+
+    def ray_order_buffer(self, count: int) -> dict:
+        """arx_debug_ray_order_buffer: the first count slots (count x 4 floats) of the current frame
+        set's direction buffer, the ray id of slot 0, the leading slots still in ray order and whether
+        the pool's slots are sorted."""
+        out = np.empty((int(count), 4), np.float32)
+        first, n_static, srt = C.c_uint64(), C.c_uint64(), C.c_int32()
+        check(lib().arx_debug_ray_order_buffer(self.handle, fptr(out), int(count), C.byref(first), C.byref(n_static),
+                                               C.byref(srt)))
+        return {"dirs": out, "first_ray": int(first.value), "n_static": int(n_static.value), "sorted": bool(srt.value)}
+
     def node_images(self) -> dict:
         """Parity hook (arx_debug_node_images): the device's coded f32 nodes (n x 16 words), their
         device-made 16-bit quantized copy (n x 8 words), the grid and the re-quantization count."""

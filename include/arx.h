@@ -522,6 +522,44 @@ arx_status arx_debug_group_force_collectives(arx_group* g, int32_t on, int32_t o
  * broadcasts (rank path). */
 arx_status arx_debug_group_collectives(const arx_group* g, uint64_t* out3);
 
+/* The ray direction buffer across launches, and the order the ray pool hands rays out in.
+ *
+ * A ray's direction is a pure function of (seed, ray id), so each frame set keeps the float4
+ * directions its last trace launch used and the next launch re-makes them only when the seed, the
+ * first ray or the ray count differ, when the buffer had to grow (a larger launch reallocates it
+ * and forgets its content), or when arx_set_stream named another stream since.  Nothing else invalidates the directions: not the scene, the emitter, the
+ * listener or the thresholds.
+ *
+ * Launches large enough for the ray pool (arx_stats.trace_grid_cus; 16-bit nodes, LDS stack) also
+ * order the pool's part of the buffer longest ray first: the first such launch of a key runs a
+ * measuring instance of the trace kernel (same rays, arithmetic and results; it also stores each
+ * ray's node + leaf steps, and the largest count for a ray that ended on the receiver: its length
+ * changes with the listener, so it starts first), a device counting sort by descending cost follows
+ * on the same stream, and the launches after it hand out the sorted buffer for as long as the key
+ * holds.  The key is all that
+ * moves a ray's path: the scene (every arx_set_scene, and the tree hash), emitter, seed, ray range,
+ * max_bounces, energy threshold, IR length (distance limit), base power and ray count (initial
+ * energy), hrtf_absorption_rate, is_mono, the kernel instance and the pool's share.  The listener's
+ * position and yaw are not in it.  A changed key measures and sorts again.  The int64 histogram and
+ * the counters do not depend on the order rays run in, so every mode gives the same bits.
+ *
+ * mode 0: directions kept, always in ray order (no measuring, no sort);
+ * mode 1: the above;
+ * mode 2: directions re-made by every launch, in ray order (nothing kept).
+ * Takes effect at the next trace launch of each frame set. */
+arx_status arx_debug_set_ray_order(arx_renderer* r, int32_t mode);
+/* Tests only (synchronises): the first `count` float4 slots (x, y, z, 0) of the current frame set's
+ * direction buffer as its last launch left it, the ray id of slot 0 in ray order, the number of
+ * leading slots still in ray order (the static ranges; all of them when the buffer is not sorted) and
+ * whether the pool's slots are sorted. */
+arx_status arx_debug_ray_order_buffer(arx_renderer* r, float* h_out_xyzw, uint64_t count, uint64_t* first_ray,
+                                      uint64_t* n_static, int32_t* sorted);
+/* Host only: the helpers the trace kernel and the pool's sort share -- the statically dealt rays of a
+ * launch of n with dyn_share / 256 of them in the pool, a step count as the measuring instance stores
+ * it (saturated to 16 bits), and this build's dyn_share.  Any output may be NULL. */
+arx_status arx_debug_ray_order_host(uint64_t n, uint32_t dyn_share, uint32_t steps, uint64_t* n_static, uint32_t* cost16,
+                                    uint32_t* build_share);
+
 /* Debug / parity hooks. */
 arx_status arx_debug_ray_directions(uint64_t seed, uint64_t first_ray, uint64_t count, float* h_out_xyz,
                                     int device);
