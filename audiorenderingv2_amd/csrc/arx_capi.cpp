@@ -381,6 +381,7 @@ void arx_destroy(arx_renderer* r) {
     hipFree(r->d_wbuf);
     hipFree(r->d_w4f);
     hipFree(r->d_tree_flag);
+    free_path_cache(r->path_cache);
     if (r->h_tree_flag) hipHostFree(r->h_tree_flag);
     hipFree(r->d_conv_in);
     hipFree(r->d_conv_out);
@@ -476,6 +477,9 @@ arx_status arx_set_frames_in_flight(arx_renderer* r, int32_t n) {
     std::swap(r->sets[0], r->sets[r->slot]);  // the current set stays, as set 0
     r->slot = 0;
     r->last_conv = r->last_reduced = r->last_scene = -1;
+    // the path cache's records name the stream that made them and the sets that replayed them
+    r->path_cache.recorded = r->path_cache.last_valid = false;
+    for (bool& b : r->path_cache.replayed) b = false;
     for (int k = n; k < arx_renderer::kMaxFrames; ++k) free_frame_set(r->sets[k]);
     for (int k = 0; k < n; ++k)
         for (hipEvent_t* e : {&r->ev_traced[k], &r->ev_conv[k], &r->ev_reduced[k], &r->ev_scene[k]})

@@ -448,7 +448,68 @@ arx_status ensure_device_scene(arx_renderer* r) {
     return ARX_OK;
 }
 
+static_assert(kPathFrames == arx_renderer::kMaxFrames, "one last-replay event per frame set");
+
+// The path cache's buffers for a recording of n rays and `need` bytes of records: made at the first
+// recording and kept across keys; a buffer that must grow is freed once every frame set's stream is
+// idle (a replay of the key before may still read it).  *fits false: the device has no room for them (the
+// cache is optional: the caller traces the launch instead); what was freed stays freed.
+arx_status path_cache_reserve(arx_renderer* r, uint64_t n, uint64_t need, bool* fits) {
+    PathCache& pc = r->path_cache;
+    *fits = true;
+    auto room = [&](void** p, size_t bytes) {  // true: allocated; false: out of memory (error cleared)
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            *p = nullptr;
+            *fits = false;
+        }
+        return e;
+    };
+    if (!pc.ev_recorded) ARX_HIP(hipEventCreateWithFlags(&pc.ev_recorded, hipEventDisableTiming));
+    for (hipEvent_t& e : pc.ev_replayed)
+        if (!e) ARX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (!pc.d_scratch) ARX_HIP(hipMalloc(&pc.d_scratch, (kCursor + 1) * sizeof(unsigned long long)));
+    if (!pc.h_scratch) ARX_HIP(hipHostMalloc(&pc.h_scratch, kCounters * sizeof(unsigned long long), hipHostMallocDefault));
+    if (n <= pc.dirs_cap && need <= pc.cap_bytes) return ARX_OK;
+    const arx_status st = sync_renderer(r);
+    if (st != ARX_OK) return st;
+    if (n > pc.dirs_cap) {
+        hipFree(pc.d_dirs);
+        pc.d_dirs = nullptr;
+        pc.dirs_cap = 0;
+        if (const hipError_t e = room(&pc.d_dirs, n * 16); e == hipErrorOutOfMemory) return ARX_OK;
+        else ARX_HIP(e);
+        pc.dirs_cap = n;
+    }
+    if (need > pc.cap_bytes) {
+        hipFree(pc.d_hits);
+        pc.d_hits = nullptr;
+        pc.cap_bytes = 0;
+        if (const hipError_t e = room(&pc.d_hits, need); e == hipErrorOutOfMemory) return ARX_OK;
+        else ARX_HIP(e);
+        pc.cap_bytes = need;
+    }
+    return ARX_OK;
+}
+
 }  // namespace
+
+void arx::free_path_cache(PathCache& p) {
+    hipFree(p.d_dirs);
+    hipFree(p.d_hits);
+    hipFree(p.d_scratch);
+    if (p.h_scratch) hipHostFree(p.h_scratch);
+    if (p.ev_recorded) hipEventDestroy(p.ev_recorded);
+    for (hipEvent_t e : p.ev_replayed)
+        if (e) hipEventDestroy(e);
+    const int32_t mode = p.mode;
+    const uint64_t max_bytes = p.max_bytes;
+    p = PathCache{};
+    p.mode = mode;
+    p.max_bytes = max_bytes;
+    p.state = mode == 1 ? kPathTraced : kPathOff;
+}
 
 arx_status arx::set_scene_image(arx_renderer* r, SceneRef img) {
     const char* why = "";
@@ -629,6 +690,97 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     const bool shared_grid = r->fif >= 2 && !small && !gstack && !a.wbuf;
     const int grid_cus = shared_grid ? std::max(1, r->cus * ARX_SHARED_GRID_PCT / 100) : r->cus;
     r->stats.trace_grid_cus = grid_cus;
+    // The path cache (arx_debug_set_path_cache, include/arx.h).  A launch whose key equals the previous
+    // launch's, on a direction buffer in its final state (one this launch would neither fill nor
+    // measure), records the scene-only hits and replays them; the launches of that key after it only
+    // replay.  Everything else is traced as above and costs what it did.
+    PathCache& pc = r->path_cache;
+    const bool cacheable = pc.mode == 1 && r->stream == f.stream && trace_can_cache(a, r->force_global_stack);
+    bool replay = false, record = false;
+    if (pc.mode != 1) {
+        pc.state = kPathOff;
+        pc.recorded = pc.last_valid = false;
+    } else if (!cacheable) {
+        pc.state = kPathNotCacheable;
+        pc.recorded = pc.last_valid = false;
+    } else {
+        OrderKey pk = key;
+        if (!ordered) {
+            pk.scene_gen = r->scene_gen;
+            pk.tree_hash = r->stats.tree_hash;
+            pk.seed = c.seed;
+            pk.ray_begin = ray_begin;
+            pk.ray_end = ray_end;
+            for (int k = 0; k < 3; ++k) pk.emitter[k] = r->emitter[k];
+            pk.e0 = a.e0;
+            pk.energy_thres = a.energy_thres;
+            pk.hrtf = a.hrtf;
+            pk.dist_limit = a.dist_limit;
+            pk.max_bounces = a.max_bounces;
+            pk.is_mono = a.is_mono;
+        }
+        pk.dyn_share = 0;  // the cache carries its own directions: neither shapes a ray's path
+        pk.instance = 0;
+        const bool repeated = pc.last_valid && std::memcmp(&pk, &pc.last_key, sizeof(pk)) == 0;
+        if (pc.recorded && std::memcmp(&pk, &pc.key, sizeof(pk)) != 0) pc.recorded = false;
+        pc.last_key = pk;
+        pc.last_valid = true;
+        pc.state = kPathTraced;
+        const bool final_dirs = !fill_dirs && !measure;
+        const uint64_t need = arx_debug_path_cache_bytes(n_launch, a.max_bounces);
+        if (need > pc.max_bytes || (pc.no_room > 0 && need >= pc.no_room)) {  // over the cap, or known not to fit
+            pc.state = kPathOverCap;
+            pc.recorded = false;
+        } else if (final_dirs && pc.recorded) {
+            replay = true;
+        } else if (final_dirs && repeated) {
+            record = replay = true;
+        }
+        if (record) {
+            bool fits = true;
+            if ((st = path_cache_reserve(r, n_launch, need, &fits)) != ARX_OK) return st;
+            if (fits) {
+                pc.key = pk;
+            } else {  // no room on the device for an optional cache: this launch is traced like an over-cap one
+                record = replay = false;
+                pc.state = kPathOverCap;
+                pc.no_room = need;  // not tried again per frame (arx_debug_set_path_cache forgets it)
+            }
+        }
+    }
+    if (replay) {
+        TraceArgs pa = a;
+        pa.dirs = pc.d_dirs;
+        pa.rec = pc.d_hits;
+        if (record) {
+            // the cache may still be read by the other sets' replays of the key before
+            for (int k = 0; k < r->fif; ++k)
+                if (pc.replayed[k] && k != r->slot) ARX_HIP(hipStreamWaitEvent(r->stream, pc.ev_replayed[k], 0));
+            for (bool& b : pc.replayed) b = false;
+            ARX_HIP(hipMemcpyAsync(pc.d_dirs, f.d_dirs, n_launch * 16, hipMemcpyDeviceToDevice, r->stream));
+            TraceArgs ra = pa;
+            ra.hist = nullptr;
+            ra.counters = pc.d_scratch;
+            ra.cursor = pc.d_scratch + kCursor;
+            ra.clear_bins = 0;
+            ra.clear_counters = kCounters;
+            ARX_HIP(launch_path_record(ra, grid_cus, r->stream));
+            pc.recorded = true;
+            pc.bytes = kPathRecordBytes * (uint64_t)a.max_bounces * n_launch;
+            pc.rec_stream = r->stream;
+            ARX_HIP(hipEventRecord(pc.ev_recorded, r->stream));
+        } else if (pc.rec_stream != r->stream) {
+            ARX_HIP(hipStreamWaitEvent(r->stream, pc.ev_recorded, 0));
+        }
+        ARX_HIP(launch_path_replay(pa, r->stream));
+        if (r->fif > 1) {
+            ARX_HIP(hipEventRecord(pc.ev_replayed[r->slot], r->stream));
+            pc.replayed[r->slot] = true;
+        }
+        pc.state = record ? kPathRecorded : kPathReplayed;
+        if (timed && (st = r->trace_ring.end(r->stream)) != ARX_OK) return st;
+        return fif_done_traced(r);
+    }
     f.dirs_valid = false;  // until the launches below are issued
     ARX_HIP(launch_trace(a, grid_cus, r->stream, r->force_global_stack, fill_dirs));
     f.dirs_stream = r->stream;
@@ -854,6 +1006,39 @@ arx_status arx_debug_set_ray_order(arx_renderer* r, int32_t mode) {
     if (!r || mode < 0 || mode > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "ray order: 0, 1 or 2");
     r->ray_order = mode;
     return ARX_OK;
+}
+
+arx_status arx_debug_set_path_cache(arx_renderer* r, int32_t mode, uint64_t max_bytes) {
+    if (!r || mode < 0 || mode > 1) return fail(ARX_ERR_INVALID_ARGUMENT, "path cache: mode 0 or 1");
+    PathCache& pc = r->path_cache;
+    pc.mode = mode;
+    pc.max_bytes = max_bytes;
+    pc.recorded = pc.last_valid = false;  // the next launch is traced
+    pc.no_room = 0;
+    pc.state = mode == 1 ? kPathTraced : kPathOff;
+    return ARX_OK;
+}
+
+arx_status arx_debug_path_cache_state(arx_renderer* r, int32_t* state, uint64_t* bytes, uint64_t* queries_recorded) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    const PathCache& pc = r->path_cache;
+    if (state) *state = pc.state;
+    if (bytes) *bytes = pc.recorded ? pc.bytes : 0;
+    if (queries_recorded) {
+        *queries_recorded = 0;
+        if (pc.recorded) {  // the recording's own query counter (its scratch block)
+            ARX_HIP(hipSetDevice(r->cfg.device));
+            ARX_HIP(hipMemcpyAsync(pc.h_scratch, pc.d_scratch, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                   pc.rec_stream));
+            ARX_HIP(hipStreamSynchronize(pc.rec_stream));
+            *queries_recorded = pc.h_scratch[0];
+        }
+    }
+    return ARX_OK;
+}
+
+uint64_t arx_debug_path_cache_bytes(uint64_t n_rays, uint32_t max_bounces) {
+    return kPathRecordBytes * n_rays * (uint64_t)max_bounces;
 }
 
 arx_status arx_debug_ray_order_buffer(arx_renderer* r, float* h_out_xyzw, uint64_t count, uint64_t* first_ray,

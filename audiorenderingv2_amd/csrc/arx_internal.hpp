@@ -101,6 +101,42 @@ struct OrderKey {
     uint32_t max_bounces, dyn_share;
     int32_t is_mono, instance;
 };
+// The path cache (arx_debug_set_path_cache, include/arx.h): the scene-only closest hit of every query
+// of every ray of one key, recorded by the second consecutive launch of that key and replayed against
+// the receiver by the launches after it (trace_rays, arx_capi_trace.cpp).  The key is an OrderKey
+// without dyn_share and instance, valid for every 16-bit LDS-stack launch: the cache carries its own
+// copy of the direction buffer it was recorded on, so neither the pool's share nor a frame set's own
+// scatter order matters to it.  One per renderer, shared by its frame sets.
+#ifndef ARX_PATH_CACHE_DEFAULT
+#define ARX_PATH_CACHE_DEFAULT 1  // build.py --exp with 0: the cache-off library (A/B partner)
+#endif
+constexpr int kPathOff = 0, kPathTraced = 1, kPathRecorded = 2, kPathReplayed = 3, kPathNotCacheable = 4,
+              kPathOverCap = 5;  // arx_debug_path_cache_state
+constexpr int kPathFrames = 3;    // arx_renderer::kMaxFrames
+struct PathCache {
+    int32_t mode = ARX_PATH_CACHE_DEFAULT;
+    uint64_t max_bytes = 1ull << 30;
+    int32_t state = ARX_PATH_CACHE_DEFAULT ? kPathTraced : kPathOff;  // of the last launch
+    OrderKey key{};        // of the records (recorded) ...
+    bool recorded = false;
+    OrderKey last_key{};   // ... and of the previous launch (last_valid), whatever ran for it
+    bool last_valid = false;
+    void* d_dirs = nullptr;       // the direction buffer the records index, 16 B per ray
+    void* d_hits = nullptr;       // [bounce][slot] 16-B records, then [bounce][slot] 8-B records
+    uint64_t cap_bytes = 0;       // of d_hits
+    uint64_t dirs_cap = 0;        // rays of d_dirs
+    uint64_t bytes = 0;           // of the records in use (recorded)
+    uint64_t no_room = 0;         // > 0: records of this size did not fit on the device (treated as over the cap)
+    unsigned long long* d_scratch = nullptr;  // the recording's counters and pool cursor (kCursor + 1 words)
+    unsigned long long* h_scratch = nullptr;  // pinned, kCounters words
+    hipStream_t rec_stream = nullptr;         // the stream of the recording
+    // frames in flight: a replay on another set's stream waits for `recorded`; a new recording waits
+    // for every set's last replay
+    hipEvent_t ev_recorded = nullptr, ev_replayed[kPathFrames] = {};
+    bool replayed[kPathFrames] = {};
+};
+void free_path_cache(PathCache& p);
+
 // A ring of (start, end) event pairs around the last kTraceRing timed launches of one kind.  A launch
 // that is not timed records nothing and does not advance the ring.
 constexpr int kTraceRing = 256;
@@ -197,6 +233,7 @@ struct arx_renderer {
     int32_t occ[3][3][3] = {};     // per node format and instance (kInstPool, kInstSmall, kInstMeasure): VGPRs, waves admitted, waves targeted
     int32_t ray_order = ARX_RAY_ORDER_DEFAULT;  // arx_debug_set_ray_order: 0 identity, directions kept; 1 longest-first pool; 2 directions re-made per launch
     uint64_t scene_gen = 0;        // scenes installed (set_scene_image): part of a frame set's OrderKey
+    arx::PathCache path_cache;     // scene-only hits of the last repeated key (arx_debug_set_path_cache)
     arx::QGrid qgrid{};
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)

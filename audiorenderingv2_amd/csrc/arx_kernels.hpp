@@ -29,6 +29,16 @@ uint32_t trace_pool_share();
 hipError_t launch_order_pool(const void* dirs_in, void* dirs_out, const unsigned short* cost, uint32_t* bins, uint64_t n,
                              hipStream_t s);
 size_t order_bins_bytes();
+// The path cache (arx_renderer::PathCache).  trace_can_cache: the launch takes a 16-bit LDS-stack
+// instance, pool or small -- the ones with a recording instance.  launch_path_record: that instance's
+// recording twin over the scene alone, on a.dirs as it stands (no directions are made), storing every
+// query's closest hit into a.rec; a.counters (a.clear_counters of them zeroed first)
+// and a.cursor must be a scratch block, a.hist is not touched.  launch_path_replay: the frame from
+// those records and the receiver sub-tree (replay_kernel), with the clear a.clear_bins /
+// a.clear_counters ask for in front; a.dirs must be the buffer the records were made on.
+bool trace_can_cache(const TraceArgs& a, bool force_global_stack);
+hipError_t launch_path_record(const TraceArgs& a, int cus, hipStream_t s);
+hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s);
 // Lanes of the largest persistent trace grid (columns of the global traversal stack).
 inline uint64_t trace_max_lanes(int cus) { return (uint64_t)(cus > 0 ? cus : 256) * 2048ull; }
 // i64 histogram -> f32 IR (+ mono merge); unit = e0 * 2^-frac_bits.

@@ -148,8 +148,18 @@ struct TraceArgs {
     uint32_t dyn_chunk;          // rays per pool atomic
     uint64_t clear_bins;         // > 0: the direction pre-pass also zeroes hist[0, clear_bins) ...
     int32_t clear_counters;      // ... and counters[0, clear_counters) (render(): no separate clear launch)
-    unsigned short* cost;        // per direction-buffer slot, the steps of its ray (the measuring instance only; null otherwise)
+    // One word for two exclusive uses, so the argument block (and with it the product instances'
+    // machine code, which addresses the hidden arguments behind it) keeps its size:
+    union {
+        unsigned short* cost;    // per direction-buffer slot, the steps of its ray (the measuring instance only; null otherwise)
+        // The path cache (recording instance and replay kernel only): the scene-only closest hit of the
+        // query of slot s at bounce b is record b * n + s, n = ray_end - ray_begin, of two planes --
+        // max_bounces * n records of 16 B (t, id, unit, v), then as many of 8 B (w, det).
+        void* rec;
+    };
 };
+constexpr uint64_t kPathRecordBytes = 24;
+static_assert(sizeof(TraceArgs) == 240, "TraceArgs: the product kernels' hidden arguments start at this offset");
 
 // Rays of a launch of n dealt out statically (slots [0, n_static) of the direction buffer, one range
 // per wave); the other n * dyn_share / 256 form the pool (trace_kernel).  The kernel and the host's

@@ -288,7 +288,10 @@ __device__ __forceinline__ void ray_init(const TraceArgs& a, RayState& s, uint64
 }
 
 // __closesthit__radiance (devicePrograms.cu:62-180) for TriRec `hit`, or __miss__radiance
-// (:186-190) when hit < 0.  r is the ray the query was traced with.
+// (:186-190) when hit < 0.  r is the ray the query was traced with.  HIST false (the path cache's recording
+// instance): a hit on a receiver-marked triangle ends the ray and counts as everywhere else, but adds
+// nothing to the histogram, which that instance does not have.
+template <bool HIST = true>
 __device__ __forceinline__ void shade(const TraceArgs& a, const float4* __restrict__ tbase, RayState& s, const Ray& r,
                                       const Best& best, uint32_t& n_rx, uint32_t& n_miss) {
     const int hit = best.unit;
@@ -337,7 +340,7 @@ __device__ __forceinline__ void shade(const TraceArgs& a, const float4* __restri
     if (ab == -1.0f || ab == -2.0f) {  // receiver halves (:128-170)
         ++n_rx;
         const int k = (int)roundf((s.dist / (float)kSpeedOfSound) * (float)a.sample_rate);
-        if (k < a.ir_len) {
+        if (HIST && k < a.ir_len) {
             unsigned long long* hl = a.hist;
             unsigned long long* hr = a.hist + a.ir_len;
             unsigned long long* own = (ab == -1.0f) ? hl : hr;
@@ -457,7 +460,9 @@ __device__ __forceinline__ uint4 node_half(__amdgpu_buffer_rsrc_t rs, int node, 
 //        origins on the grid, far below the 0.1-step outward margin of every quantized plane
 //        (quantize_nodes16; the launcher checks the emitter is on the grid).
 //   f32: the coded BvhNode (56 of its 64 B), ix = inv, oix = o*inv.
-template <int FMT, typename Stack, bool PIN = true>
+//   SKIP0: child 0 counts as missed whatever its box (replay_kernel enters the receiver sub-tree by a
+//   step on the top node that leaves the scene, child 0, alone).
+template <int FMT, typename Stack, bool PIN = true, bool SKIP0 = false>
 __device__ __forceinline__ void node_step(const Ray& r, float oix, float oiy, float oiz, Trav& t, const Stack& stk,
                                           __amdgpu_buffer_rsrc_t rs, const uint4* __restrict__ ncache,
                                           arx_i32x4 qrs) {
@@ -565,7 +570,7 @@ __device__ __forceinline__ void node_step(const Ray& r, float oix, float oiy, fl
         tn1 = fmaxf(fmaxf(fminf(x10, x11), fminf(y10, y11)), fmaxf(fminf(z10, z11), 0.0f));
         tf1 = fminf(fminf(fmaxf(x10, x11), fmaxf(y10, y11)), fminf(fmaxf(z10, z11), t.best.t));
     }
-    const bool h0 = tn0 <= tf0, h1 = tn1 <= tf1;
+    const bool h0 = SKIP0 ? false : tn0 <= tf0, h1 = tn1 <= tf1;
     const bool near1 = h1 & (!h0 | (tn1 < tn0));
     const int c_near = near1 ? c1 : c0;
     const int c_far = near1 ? c0 : c1;
@@ -777,8 +782,16 @@ constexpr int kDynShare = ARX_TRACE_DYN_SHARE, kDynChunk = ARX_TRACE_DYN_CHUNK, 
 // the direction-buffer index the lane took at refill.  The
 // launcher orders the pool's slots by that cost for the following launches (launch_order_pool).  Same
 // rays, same arithmetic, same counters as the product instance, whose code this parameter leaves alone.
+// RECORD (the path cache's recording instance, 16-bit nodes and LDS stack, pool or small): every query
+// runs over the scene alone -- it starts at the top node's child 0, so the receiver is never a candidate
+// and no ray ends on it -- and its final closest hit is stored at a.rec_*[depth * n + slot] before
+// shade(), a miss too (unit -1).  The launcher points a.counters and a.cursor at a scratch block and
+// passes no histogram: a scene may hold receiver-marked triangles of its own (absorption -1 / -2 is
+// valid scene input), which end a ray here as they do in a traced frame, so this instance shades with
+// shade<false>, which adds nothing to the histogram; the replay adds such a hit's energy from the
+// record, with the frame's histogram.  replay_kernel answers the following launches of the same key.
 template <int BLOCK, int THRESH, int LEAF_THRESH, int MINW, int NSTEPS, int FMT, bool GSTACK, bool LEAN = false,
-          bool MEASURE = false>
+          bool MEASURE = false, bool RECORD = false>
 __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
     constexpr bool Q16 = FMT == kFmtQ16;
     constexpr bool W4 = FMT == kFmtW4;
@@ -869,6 +882,8 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
     t.sp = 0;
     float oix = 0.f, oiy = 0.f, oiz = 0.f;
     uint32_t m_slot = 0u, m_cost = 0u;  // MEASURE: the current ray's buffer slot and its steps so far
+    int rec_root = 0;  // RECORD: where a query starts, the scene root's code (a leaf code in a tiny scene)
+    if constexpr (RECORD) rec_root = a.qnodes[0].c[0].code;
     while (true) {
 #if ARX_TRACE_PROF
         ++pf[10];
@@ -882,7 +897,14 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
 #endif
         if (active && (LEAN ? t.node == -1 : !trav)) {  // the query is done: shade it
             const uint32_t rx_before = n_rx;
-            shade(a, tbase, s, r, t.best, n_rx, n_miss);
+            if constexpr (RECORD) {
+                const uint64_t at = (uint64_t)s.depth * n + m_slot;
+                float4* rec_hit = reinterpret_cast<float4*>(a.rec);
+                float2* rec_bary = reinterpret_cast<float2*>(rec_hit + (uint64_t)a.max_bounces * n);
+                rec_hit[at] = make_float4(t.best.t, __int_as_float(t.best.id), __int_as_float(t.best.unit), t.best.v);
+                rec_bary[at] = make_float2(t.best.w, t.best.det);
+            }
+            shade<!RECORD>(a, tbase, s, r, t.best, n_rx, n_miss);
             if (!wants_query(a, s)) {
                 active = false;
                 // the ray retires.  One the receiver ended says nothing about its length once the
@@ -920,6 +942,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
                 if (i < w_end) {
                     ray_init(a, s, a.ray_begin + i);
                     active = wants_query(a, s);
+                    if constexpr (RECORD) m_slot = (uint32_t)i;
                     if constexpr (MEASURE) {
                         m_slot = (uint32_t)i;  // i < n <= 2^31 - 1 rays
                         m_cost = 0u;
@@ -954,7 +977,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
             t.best.t = __builtin_huge_valf();
             t.best.id = 0x7fffffff;
             t.best.unit = -1;
-            t.node = 0;  // the top node (node 0; unit 0 of the CW4 buffer)
+            t.node = RECORD ? rec_root : 0;  // the top node (node 0; unit 0 of the CW4 buffer)
             t.sp = 0;
             trav = true;
         }
@@ -1039,6 +1062,106 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
     atomicAdd(a.counters + 6, (unsigned long long)n_leader);
     atomicAdd(a.counters + 7, (unsigned long long)n_slots);
 #endif
+}
+
+// The path cache's replay (arx_capi_trace.cpp, PathCache): a frame of a key whose scene-only closest
+// hits trace_kernel<RECORD> stored.  A ray's path through the static scene does not depend on the
+// listener; the receiver enters a query only as one more candidate for the closest hit, take_hit's
+// lexicographic minimum of (t, id) does not depend on the order candidates are tested in, and a
+// receiver hit ends the ray.  So each query here is the cached hit, a closest-hit query over the
+// receiver sub-tree alone that starts from it, and the same shade(): the histogram and the counters
+// come out bit for bit as the full traversal's.  The receiver sub-tree is entered by one step on the
+// top node with child 0 (the scene) forced off: a segment that misses the receiver's box costs that
+// one step.  One ray per lane, slot = lane's global index into the cache's own direction copy
+// (a.dirs); a plain grid, every lane's work about the same, so no pool and no persistent waves.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void replay_kernel(TraceArgs a) {
+    __shared__ int stk_lds[(kLdsStack + 1) * BLOCK];
+    __shared__ uint4 ncache[kNodeCache > 0 ? 2 * kNodeCache : 1];  // node_step's top-of-tree copy, as in trace_kernel
+    if constexpr (kNodeCache > 0) {
+        const uint4* q = reinterpret_cast<const uint4*>(a.qnodes);
+        for (int i = threadIdx.x; i < 2 * kNodeCache; i += BLOCK) ncache[i] = q[i];
+        __syncthreads();
+    }
+    using Stack = LdsStack<BLOCK, kLdsStack>;
+    const int lane = threadIdx.x;
+    Stack stk;
+    stk.base = stk_lds + lane;
+    stk_lds[lane] = -1;  // the dummy row under the stack (LdsStack::kSentinel)
+    const __amdgpu_buffer_rsrc_t nrs = buffer_rsrc(a.qnodes, ARX_TRACE_IDXEN ? (short)sizeof(QNode2) : (short)0);
+    arx_i32x4 qrs;
+    {
+        const unsigned long long qa = (unsigned long long)a.qnodes;
+        qrs.x = (int)(uint32_t)qa;
+        qrs.y = (int)((qa >> 32) & 0xffffu);
+        qrs.z = 0x7fffffff;
+        qrs.w = 0x00020000;
+    }
+    const float4* tbase = reinterpret_cast<const float4*>(a.tris);
+    const __amdgpu_buffer_rsrc_t trs = buffer_rsrc(tbase);
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const float4* __restrict__ rec_hit = reinterpret_cast<const float4*>(a.rec);
+    const float2* __restrict__ rec_bary = reinterpret_cast<const float2*>(rec_hit + (uint64_t)a.max_bounces * n);
+    const uint64_t slot = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t n_q = 0, n_rx = 0, n_miss = 0;
+    RayState s;
+    s.depth = -1;
+    bool active = false;
+    if (slot < n) {
+        ray_init(a, s, a.ray_begin + slot);
+        active = wants_query(a, s);
+    }
+    Ray r;
+    Trav t;
+    while (__ballot(active) != 0ull) {
+        float oix = 0.f, oiy = 0.f, oiz = 0.f;
+        t.node = -1;
+        t.sp = 0;
+        if (active) {
+            // (fetching the next bounce's record a query ahead measured even: the load is not what a
+            // query waits for, profiles/r10/ab_path_cache.txt)
+            const uint64_t at = (uint64_t)s.depth * n + slot;
+            const float4 h = rec_hit[at];
+            const float2 b = rec_bary[at];
+            t.best.t = h.x;
+            t.best.id = __float_as_int(h.y);
+            t.best.unit = __float_as_int(h.z);
+            t.best.v = h.w;
+            t.best.w = b.x;
+            t.best.det = b.y;
+            ++n_q;
+            setup_ray(r, s.pos, s.dir);
+            oix = (r.o[0] - a.qgrid.origin[0]) * r.inv[0];
+            oiy = (r.o[1] - a.qgrid.origin[1]) * r.inv[1];
+            oiz = (r.o[2] - a.qgrid.origin[2]) * r.inv[2];
+            r.inv[0] *= a.qgrid.scale[0];
+            r.inv[1] *= a.qgrid.scale[1];
+            r.inv[2] *= a.qgrid.scale[2];
+#if ARX_TRACE_SIGNSEL && ARX_TRACE_BITFLOAT
+            oix = __builtin_fmaf(8388608.0f, r.inv[0], oix);
+            oiy = __builtin_fmaf(8388608.0f, r.inv[1], oiy);
+            oiz = __builtin_fmaf(8388608.0f, r.inv[2], oiz);
+#endif
+            // the top node, the scene's child off: on to the receiver's root or done
+            t.node = 0;
+            node_step<kFmtQ16, Stack, false, true>(r, oix, oiy, oiz, t, stk, nrs, ncache, qrs);
+        }
+        while (true) {  // the receiver sub-tree: node steps while any lane has one, then the pending leaves
+            const unsigned long long m_node = __ballot(t.node >= 0);
+            const unsigned long long m_leaf = __ballot(t.node <= -2);
+            if ((m_node | m_leaf) == 0ull) break;
+            if (m_node != 0ull) {
+                if (t.node >= 0) node_step<kFmtQ16, Stack, false>(r, oix, oiy, oiz, t, stk, nrs, ncache, qrs);
+            } else {
+                leaf_step<kFmtQ16>(trs, r, t, stk);
+            }
+        }
+        if (active) {
+            shade(a, tbase, s, r, t.best, n_rx, n_miss);
+            active = wants_query(a, s);
+        }
+    }
+    flush_counters(a, n_q, n_rx, n_miss, lane);
 }
 
 __global__ void finalize_ir_kernel(const long long* __restrict__ hist, float* __restrict__ L, float* __restrict__ R,
@@ -1316,6 +1439,54 @@ bool trace_can_measure(const TraceArgs& a, int cus, bool force_global_stack) {
 }
 
 uint32_t trace_pool_share() { return (uint32_t)kDynShare; }
+
+bool trace_can_cache(const TraceArgs& a, bool force_global_stack) {
+    if (a.ray_end <= a.ray_begin || a.wbuf || !a.qnodes) return false;
+    return !(force_global_stack || a.bvh_depth + 1 > kLdsStack);
+}
+
+hipError_t launch_path_record(const TraceArgs& a, int cus, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.counters || !a.cursor || !a.rec)
+        return hipErrorInvalidValue;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    TraceArgs a2 = a;
+    const bool dyn = uses_pool<kFmtQ16, false>(a, cus);
+    a2.dyn_share = dyn ? (uint32_t)kDynShare : 0u;
+    a2.dyn_chunk = (uint32_t)kDynChunk;
+    // the pre-pass without directions or histogram: the scratch counters and the pool cursor zeroed
+    hipLaunchKernelGGL(dirs_kernel, dim3(1), dim3(256), 0, s, a.seed, a.ray_begin, (uint64_t)0,
+                       reinterpret_cast<float4*>(const_cast<void*>(a.dirs)), a.cursor, (unsigned long long*)nullptr,
+                       (uint64_t)0, a.counters, a.clear_counters);
+    if (kSmallBlock > 0 && !dyn) {
+        constexpr int SB = kSmallBlock > 0 ? kSmallBlock : kBlock;
+        const int g2 = trace_grid<SB, false, kFmtQ16>(a, cus, n_rays);
+        hipLaunchKernelGGL((trace_kernel<SB, kThresh, kSmallLeaf, kSmallWaves, kSmallSteps, kFmtQ16, false, true, false, true>),
+                           dim3(g2), dim3(SB), 0, s, a2);
+    } else {
+        const int grid = trace_grid<kBlock, false, kFmtQ16>(a, cus, n_rays);
+        hipLaunchKernelGGL((trace_kernel<kBlock, kThresh, kLeafThresh, kWaves, kSteps, kFmtQ16, false, false, false, true>),
+                           dim3(grid), dim3(kBlock), 0, s, a2);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.hist || !a.counters || !a.rec)
+        return hipErrorInvalidValue;
+    if (a.clear_bins > 0 || a.clear_counters > 0) {
+        const hipError_t e = launch_clear(a.hist, a.clear_bins, a.counters, a.clear_counters, s);
+        if (e != hipSuccess) return e;
+    }
+#ifndef ARX_REPLAY_BLOCK
+#define ARX_REPLAY_BLOCK 256  // design experiments only (build.py --exp)
+#endif
+    constexpr int RB = ARX_REPLAY_BLOCK;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    hipLaunchKernelGGL(replay_kernel<RB>, dim3((unsigned)((n_rays + RB - 1) / RB)), dim3(RB), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_order_pool(const void* dirs_in, void* dirs_out, const unsigned short* cost, uint32_t* bins, uint64_t n,
                              hipStream_t s) {

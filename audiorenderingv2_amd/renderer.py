@@ -222,6 +222,20 @@ class AudioRenderer:
         longest ray first, 2 directions re-made by every launch."""
         check(lib().arx_debug_set_ray_order(self.handle, int(mode)))
 
+    PATH_CACHE_STATES = ("off", "traced", "recorded", "replayed", "not-cacheable", "over-cap")
+
+    def set_path_cache(self, mode: int, max_bytes: int = 1 << 30) -> None:
+        """arx_debug_set_path_cache: 0 off, 1 (default) a repeated key replays its cached scene-only
+        hits against the receiver; max_bytes caps the records."""
+        check(lib().arx_debug_set_path_cache(self.handle, int(mode), int(max_bytes)))
+
+    def path_cache_state(self, queries: bool = False) -> dict:
+        """arx_debug_path_cache_state: what the last trace launch did (PATH_CACHE_STATES), the bytes of
+        records held and, when asked for (synchronises), the queries the recording ran."""
+        st, nb, nq = C.c_int32(), C.c_uint64(), C.c_uint64()
+        check(lib().arx_debug_path_cache_state(self.handle, C.byref(st), C.byref(nb), C.byref(nq) if queries else None))
+        return {"state": self.PATH_CACHE_STATES[st.value], "bytes": int(nb.value), "queries_recorded": int(nq.value)}
+
     def ray_order_buffer(self, count: int) -> dict:
         """arx_debug_ray_order_buffer: the first count slots (count x 4 floats) of the current frame
         set's direction buffer, the ray id of slot 0, the leading slots still in ray order and whether

@@ -560,6 +560,54 @@ arx_status arx_debug_ray_order_buffer(arx_renderer* r, float* h_out_xyzw, uint64
 arx_status arx_debug_ray_order_host(uint64_t n, uint32_t dyn_share, uint32_t steps, uint64_t* n_static, uint32_t* cost16,
                                     uint32_t* build_share);
 
+/* The path cache: a repeated key answers its queries from the scene-only hits of an earlier launch.
+ *
+ * A ray's path through the static scene does not depend on the listener: the receiver enters a query
+ * only as one more candidate for the closest hit (the lexicographic minimum of (t, triangle id), so
+ * the order candidates are tested in does not matter), and a receiver hit ends the ray.  The renderer
+ * therefore keeps, for one key, the scene-only closest hit of every query of every ray (24 B each,
+ * laid out [bounce][slot]) with its own copy of the direction buffer they were recorded on, and a
+ * frame of that key is one plain kernel: per query the cached hit, a closest-hit query over the
+ * receiver sub-tree alone that starts from it, and the same shading.  Histogram, IR and the queries /
+ * receiver_hits / misses counters are bit for bit those of the full traversal.
+ *
+ * The key is the ray order's (arx_debug_set_ray_order) without the kernel instance and the pool's
+ * share, and holds for every launch on 16-bit nodes and the LDS stack, ray pool or small: scene (every
+ * arx_set_scene, and the tree hash), emitter, seed, ray range, max_bounces, energy threshold, distance
+ * limit, initial energy, hrtf_absorption_rate, is_mono.  The listener and the receiver model are not
+ * in it.
+ *   - The first launch of a key is traced exactly as without the cache (and costs what it did).
+ *   - The first launch whose key equals the previous launch's, on a direction buffer this launch
+ *     neither fills nor measures, records (one scene-only pass of the trace kernel's recording
+ *     instance into the cache) and then replays: about one trace plus one replay.
+ *   - Later launches of the key only replay.  So a caller whose emitter or scene changes every frame
+ *     never records; one that moves only the listener pays two traced-cost launches (three with two
+ *     frames in flight: each set measures its own buffer first), then replays.
+ * Any key change returns to "traced" and drops the records.  Never cached, traced as before: the
+ * global stack, CW4 and f32-node paths, a caller's own stream (arx_set_stream), and launches whose
+ * records (max_bounces x rays x 24 B, plus 16 B per ray of directions; 384 MB at 1M rays x 16) exceed
+ * max_bytes (default 1 GiB) or do not fit on the device (reported as over the cap and not tried
+ * again until this call).  A scene's own receiver-marked triangles (absorption -1 / -2) are cached
+ * like any other: the recording ends a ray on them without a histogram, the replay adds their energy.
+ * The buffer is allocated at the first recording, kept across keys, and freed when it must grow and
+ * at arx_destroy.  arx_trace_times' window of a launch covers whatever ran
+ * for it; arx_stats' trace_* fields keep describing the traced instance the launch's arguments take.
+ * Throughput figures derived from arx_stats.queries count replayed queries like traced ones.
+ *
+ * mode 0: off (every launch traced); mode 1 (default): the above.  Either call drops the records. */
+arx_status arx_debug_set_path_cache(arx_renderer* r, int32_t mode, uint64_t max_bytes);
+#define ARX_PATH_OFF 0
+#define ARX_PATH_TRACED 1
+#define ARX_PATH_RECORDED 2      /* recorded by the last launch (which also replayed) */
+#define ARX_PATH_REPLAYED 3
+#define ARX_PATH_NOT_CACHEABLE 4
+#define ARX_PATH_OVER_CAP 5
+/* What the last trace launch did (ARX_PATH_*), the bytes of records held (0 without a recording) and
+ * the queries the recording ran (synchronises when asked for).  Any output may be NULL. */
+arx_status arx_debug_path_cache_state(arx_renderer* r, int32_t* state, uint64_t* bytes, uint64_t* queries_recorded);
+/* Host only: bytes of records for n_rays x max_bounces queries. */
+uint64_t arx_debug_path_cache_bytes(uint64_t n_rays, uint32_t max_bounces);
+
 /* Debug / parity hooks. */
 arx_status arx_debug_ray_directions(uint64_t seed, uint64_t first_ray, uint64_t count, float* h_out_xyz,
                                     int device);
