@@ -153,6 +153,10 @@ SIGNATURES = {
     "arx_debug_set_path_cache": (C.c_int, [_P, C.c_int32, C.c_uint64]),
     "arx_debug_path_cache_state": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "arx_debug_path_cache_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "arx_debug_set_path_filter": (C.c_int, [_P, C.c_int32]),
+    "arx_debug_path_filter_state": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint64)]),
+    "arx_debug_path_filter_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
     "arx_debug_set_trace_path": (C.c_int, [_P, C.c_int]),
     "arx_debug_set_refit_pad": (C.c_int, [_P, C.c_float]),
     "arx_debug_check_tree_limits": (C.c_int, [C.c_uint64, C.c_uint64]),

@@ -163,6 +163,7 @@ void free_frame_set(arx_renderer::FrameSet& f) {
     hipFree(f.d_dirs_alt);
     hipFree(f.d_cost);
     hipFree(f.d_order_bins);
+    hipFree(f.d_filter_list);
     if (f.h_counters) hipHostFree(f.h_counters);
     free_acoustics(f.acou);
     f = arx_renderer::FrameSet{};
@@ -478,7 +479,7 @@ arx_status arx_set_frames_in_flight(arx_renderer* r, int32_t n) {
     r->slot = 0;
     r->last_conv = r->last_reduced = r->last_scene = -1;
     // the path cache's records name the stream that made them and the sets that replayed them
-    r->path_cache.recorded = r->path_cache.last_valid = false;
+    r->path_cache.recorded = r->path_cache.last_valid = r->path_cache.last_filtered = false;
     for (bool& b : r->path_cache.replayed) b = false;
     for (int k = n; k < arx_renderer::kMaxFrames; ++k) free_frame_set(r->sets[k]);
     for (int k = 0; k < n; ++k)

@@ -493,20 +493,76 @@ arx_status path_cache_reserve(arx_renderer* r, uint64_t n, uint64_t need, bool* 
     return ARX_OK;
 }
 
+// The path filter's planes for a recording of n rays (outside the cap, optional).  False: no room on the
+// device (the error cleared; that size is not tried again), and the launch records and replays
+// unfiltered.  Called behind path_cache_reserve: a buffer that must grow is freed with every stream idle.
+bool path_filter_reserve(arx_renderer* r, uint64_t n, uint32_t max_bounces) {
+    PathCache& pc = r->path_cache;
+    const uint64_t need = path_filter_plane_bytes(n, max_bounces);
+    if (need <= pc.filter_cap) return true;
+    if (pc.filter_no_room > 0 && need >= pc.filter_no_room) return false;
+    if (sync_renderer(r) != ARX_OK) return false;
+    hipFree(pc.d_filter);
+    pc.d_filter = nullptr;
+    pc.filter_cap = 0;
+    if (hipMalloc(&pc.d_filter, need) != hipSuccess) {
+        (void)hipGetLastError();
+        pc.d_filter = nullptr;
+        pc.filter_no_room = need;
+        return false;
+    }
+    pc.filter_cap = need;
+    return true;
+}
+
+// The current frame set's candidate list for n rays; false as above (the frame replays unfiltered).
+bool path_filter_list_reserve(arx_renderer* r, uint64_t n) {
+    PathCache& pc = r->path_cache;
+    arx_renderer::FrameSet& f = r->cur();
+    if (n <= f.filter_list_cap) return true;
+    const uint64_t need = path_filter_list_bytes(n);
+    if (pc.filter_list_no_room > 0 && need >= pc.filter_list_no_room) return false;
+    if (f.d_filter_list) {  // an earlier replay on this set's stream may still write it
+        if (hipStreamSynchronize(f.stream) != hipSuccess) return false;
+        hipFree(f.d_filter_list);
+    }
+    f.d_filter_list = nullptr;
+    f.filter_list_cap = 0;
+    if (hipMalloc(&f.d_filter_list, need) != hipSuccess) {
+        (void)hipGetLastError();
+        f.d_filter_list = nullptr;
+        pc.filter_list_no_room = need;
+        return false;
+    }
+    f.filter_list_cap = n;
+    return true;
+}
+
+// The filter's margin (filter_kernel): kFilterMargin plus the slab test's own slack, 2^-18 of the
+// largest coordinate magnitude the grid spans (scene, emitter and receiver lie on it).
+float path_filter_grow(const QGrid& g) {
+    float m = 0.0f;
+    for (int k = 0; k < 3; ++k)
+        m = std::max(m, std::max(std::fabs(g.origin[k]), std::fabs(g.origin[k] + 65536.0f * g.scale[k])));
+    return kFilterMargin + std::ldexp(m, -18);
+}
+
 }  // namespace
 
 void arx::free_path_cache(PathCache& p) {
     hipFree(p.d_dirs);
     hipFree(p.d_hits);
+    hipFree(p.d_filter);
     hipFree(p.d_scratch);
     if (p.h_scratch) hipHostFree(p.h_scratch);
     if (p.ev_recorded) hipEventDestroy(p.ev_recorded);
     for (hipEvent_t e : p.ev_replayed)
         if (e) hipEventDestroy(e);
-    const int32_t mode = p.mode;
+    const int32_t mode = p.mode, filter_on = p.filter_on;
     const uint64_t max_bytes = p.max_bytes;
     p = PathCache{};
     p.mode = mode;
+    p.filter_on = filter_on;
     p.max_bytes = max_bytes;
     p.state = mode == 1 ? kPathTraced : kPathOff;
 }
@@ -695,6 +751,7 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     // measure), records the scene-only hits and replays them; the launches of that key after it only
     // replay.  Everything else is traced as above and costs what it did.
     PathCache& pc = r->path_cache;
+    pc.last_filtered = false;
     const bool cacheable = pc.mode == 1 && r->stream == f.stream && trace_can_cache(a, r->force_global_stack);
     bool replay = false, record = false;
     if (pc.mode != 1) {
@@ -764,6 +821,11 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
             ra.cursor = pc.d_scratch + kCursor;
             ra.clear_bins = 0;
             ra.clear_counters = kCounters;
+            // with the filter on, what every query starts from as well (outside the cap; without room
+            // for it, records alone as before)
+            pc.has_state = pc.filter_on && a.max_bounces >= 1 && a.max_bounces <= kFilterMaxBounces &&
+                           path_filter_reserve(r, n_launch, a.max_bounces);
+            ra.gstack = pc.has_state ? static_cast<int32_t*>(pc.d_filter) : nullptr;
             ARX_HIP(launch_path_record(ra, grid_cus, r->stream));
             pc.recorded = true;
             pc.bytes = kPathRecordBytes * (uint64_t)a.max_bounces * n_launch;
@@ -772,7 +834,31 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
         } else if (pc.rec_stream != r->stream) {
             ARX_HIP(hipStreamWaitEvent(r->stream, pc.ev_recorded, 0));
         }
-        ARX_HIP(launch_path_replay(pa, r->stream));
+        // Filtered unless the emitter lies inside the receiver's grown box: every ray would be a
+        // candidate at bounce 0, and the frame takes the unfiltered kernel, which costs what it did.
+        bool filtered = pc.filter_on && pc.has_state;
+        if (filtered) {
+            float lo[3], hi[3];
+            bool empty = false;
+            receiver_bound(r, lo, hi, &empty);
+            const float grow = 2.0f * path_filter_grow(a.qgrid);
+            bool inside = !empty;
+            for (int k = 0; k < 3; ++k) inside = inside && r->emitter[k] >= lo[k] - grow && r->emitter[k] <= hi[k] + grow;
+            filtered = !inside && path_filter_list_reserve(r, n_launch);
+        }
+        if (filtered) {
+            FilterArgs fa;
+            fa.planes = pc.d_filter;
+            fa.list = static_cast<FilterCand*>(f.d_filter_list);
+            fa.heads = fa.list + f.filter_list_cap;
+            fa.grow = path_filter_grow(a.qgrid);
+            ARX_HIP(launch_path_replay_filtered(pa, fa, r->stream));
+            pc.last_filtered = true;
+            pc.filter_slot = r->slot;
+            pc.filter_rays = n_launch;
+        } else {
+            ARX_HIP(launch_path_replay(pa, r->stream));
+        }
         if (r->fif > 1) {
             ARX_HIP(hipEventRecord(pc.ev_replayed[r->slot], r->stream));
             pc.replayed[r->slot] = true;
@@ -1035,6 +1121,52 @@ arx_status arx_debug_path_cache_state(arx_renderer* r, int32_t* state, uint64_t*
         }
     }
     return ARX_OK;
+}
+
+arx_status arx_debug_set_path_filter(arx_renderer* r, int32_t on) {
+    if (!r || on < 0 || on > 1) return fail(ARX_ERR_INVALID_ARGUMENT, "path filter: 0 or 1");
+    PathCache& pc = r->path_cache;
+    // switched on over records that came without state: they are forgotten, so the key's next launch
+    // records again, once, with it
+    if (on && !pc.filter_on && pc.recorded && !pc.has_state) pc.recorded = false;
+    if (on && !pc.filter_on) pc.filter_no_room = pc.filter_list_no_room = 0;
+    pc.filter_on = on;
+    return ARX_OK;
+}
+
+arx_status arx_debug_path_filter_state(arx_renderer* r, int32_t* filtered, uint64_t* bytes, uint64_t* candidate_rays,
+                                       uint64_t* candidate_queries) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    const PathCache& pc = r->path_cache;
+    if (filtered) *filtered = pc.last_filtered ? 1 : 0;
+    if (bytes) {
+        *bytes = pc.filter_cap;
+        for (const arx_renderer::FrameSet& f : r->sets)
+            if (f.d_filter_list) *bytes += path_filter_list_bytes(f.filter_list_cap);
+    }
+    if (candidate_rays) *candidate_rays = 0;
+    if (candidate_queries) *candidate_queries = 0;
+    const arx_renderer::FrameSet& f = r->sets[pc.filter_slot];
+    if ((candidate_rays || candidate_queries) && pc.last_filtered && f.d_filter_list) {
+        // the heads the launch's filter blocks left behind the list: {candidate rays, candidate queries, ...}
+        std::vector<uint32_t> h(4 * path_filter_heads(pc.filter_rays));
+        ARX_HIP(hipSetDevice(r->cfg.device));
+        ARX_HIP(hipStreamSynchronize(f.stream));
+        ARX_HIP(hipMemcpy(h.data(), static_cast<const FilterCand*>(f.d_filter_list) + f.filter_list_cap,
+                          h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        uint64_t rays = 0, queries = 0;
+        for (size_t k = 0; k < h.size(); k += 4) {
+            rays += h[k];
+            queries += h[k + 1];
+        }
+        if (candidate_rays) *candidate_rays = rays;
+        if (candidate_queries) *candidate_queries = queries;
+    }
+    return ARX_OK;
+}
+
+uint64_t arx_debug_path_filter_bytes(uint64_t n_rays, uint32_t max_bounces, uint32_t n_lists) {
+    return path_filter_plane_bytes(n_rays, max_bounces) + (uint64_t)n_lists * path_filter_list_bytes(n_rays);
 }
 
 uint64_t arx_debug_path_cache_bytes(uint64_t n_rays, uint32_t max_bounces) {

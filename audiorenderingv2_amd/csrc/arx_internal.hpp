@@ -110,6 +110,9 @@ struct OrderKey {
 #ifndef ARX_PATH_CACHE_DEFAULT
 #define ARX_PATH_CACHE_DEFAULT 1  // build.py --exp with 0: the cache-off library (A/B partner)
 #endif
+#ifndef ARX_PATH_FILTER_DEFAULT
+#define ARX_PATH_FILTER_DEFAULT 1  // build.py --exp with 0: every replay unfiltered (A/B partner)
+#endif
 constexpr int kPathOff = 0, kPathTraced = 1, kPathRecorded = 2, kPathReplayed = 3, kPathNotCacheable = 4,
               kPathOverCap = 5;  // arx_debug_path_cache_state
 constexpr int kPathFrames = 3;    // arx_renderer::kMaxFrames
@@ -134,6 +137,18 @@ struct PathCache {
     // for every set's last replay
     hipEvent_t ev_recorded = nullptr, ev_replayed[kPathFrames] = {};
     bool replayed[kPathFrames] = {};
+    // The path filter (arx_debug_set_path_filter, include/arx.h): the planes of what every recorded query
+    // started from (path_filter_plane_bytes, arx_layout.hpp), outside the cap.  has_state: the records in
+    // use came with them.  The candidate lists belong to the frame sets (FrameSet::d_filter_list).
+    int32_t filter_on = ARX_PATH_FILTER_DEFAULT;
+    void* d_filter = nullptr;
+    uint64_t filter_cap = 0;          // bytes of d_filter
+    uint64_t filter_no_room = 0;      // > 0: planes of this size did not fit on the device: not tried again ...
+    uint64_t filter_list_no_room = 0; // ... and a frame set's list of this size, a mark of its own (a list is far smaller)
+    bool has_state = false;
+    bool last_filtered = false;       // the last launch replayed filtered ...
+    int32_t filter_slot = 0;          // ... on this frame set ...
+    uint64_t filter_rays = 0;         // ... over this many rays
 };
 void free_path_cache(PathCache& p);
 
@@ -314,6 +329,10 @@ struct arx_renderer {
         unsigned short* d_cost = nullptr;
         uint32_t* d_order_bins = nullptr;
         uint64_t order_cap = 0;                    // slots of d_dirs_alt and d_cost
+        // the path filter's candidate list of this set's replays (two sets replay at once on two
+        // streams): filter_list_cap entries, then the filter blocks' heads (path_filter_list_bytes)
+        void* d_filter_list = nullptr;
+        uint64_t filter_list_cap = 0;
         Acoustics acou;
     };
     int32_t fif = 1;

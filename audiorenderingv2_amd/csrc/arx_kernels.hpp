@@ -39,6 +39,11 @@ size_t order_bins_bytes();
 bool trace_can_cache(const TraceArgs& a, bool force_global_stack);
 hipError_t launch_path_record(const TraceArgs& a, int cus, hipStream_t s);
 hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s);
+// The filtered replay of a recording that stored its queries' start state (a.gstack of
+// launch_path_record pointed at the filter's planes, arx_layout.hpp): the clear, filter_kernel over
+// every slot, replay_cand_kernel over the candidates it listed.  max_bounces in [1, kFilterMaxBounces];
+// f.list and f.heads belong to the frame set whose stream s is.  Results are launch_path_replay's.
+hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, hipStream_t s);
 // Lanes of the largest persistent trace grid (columns of the global traversal stack).
 inline uint64_t trace_max_lanes(int cus) { return (uint64_t)(cus > 0 ? cus : 256) * 2048ull; }
 // i64 histogram -> f32 IR (+ mono merge); unit = e0 * 2^-frac_bits.

@@ -13,6 +13,12 @@
 #pragma once
 #include <cstdint>
 
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define ARX_HOST_DEVICE __host__ __device__
+#else
+#define ARX_HOST_DEVICE
+#endif
+
 namespace arx {
 
 struct alignas(16) TriRec {
@@ -161,14 +167,50 @@ struct TraceArgs {
 constexpr uint64_t kPathRecordBytes = 24;
 static_assert(sizeof(TraceArgs) == 240, "TraceArgs: the product kernels' hidden arguments start at this offset");
 
+// The path filter (filter_kernel / replay_cand_kernel, arx_trace.hip): what every recorded query
+// started from, so that a replayed frame runs only the queries whose segment crosses the receiver's box.
+// One allocation of three planes, laid out [bounce][slot] like the records, n = rays of the launch:
+//   segment  (max_bounces + 1) * n x 16 B  {pos.x, pos.y, pos.z, dist}: row b is the state before query
+//            b; the row after a ray's last query holds the pos and dist shade() left
+//   state    max_bounces * n x 16 B        {dir.x, dir.y, dir.z, e} before query b
+//   per ray  n x 2 B                       queries the scene-only ray ran (kFilterCount) and the flags below
+// The recording instance takes the allocation's base in TraceArgs::gstack (it runs on the LDS stack and
+// reads neither gstack nor gstack_lanes); null: it stores the records alone.
+constexpr uint32_t kFilterMaxBounces = 64;  // one bit of a candidate mask per bounce
+constexpr unsigned short kFilterCount = 0x7f;      // bits 0..6: the ray's queries, 0..64
+constexpr unsigned short kFilterMiss = 0x100;      // its last query missed
+constexpr unsigned short kFilterMarked = 0x200;    // its last hit was a receiver-marked triangle of the scene
+constexpr unsigned short kFilterWild = 0x400;      // a stored segment end lies too far from the ray's own hit point
+ARX_HOST_DEVICE inline uint64_t path_filter_seg_rows(uint32_t max_bounces) { return (uint64_t)max_bounces + 1; }
+ARX_HOST_DEVICE inline uint64_t path_filter_plane_bytes(uint64_t n, uint32_t max_bounces) {
+    return n * (16 * path_filter_seg_rows(max_bounces) + 16 * (uint64_t)max_bounces + 2);
+}
+// A candidate ray of a filtered frame: its slot and the bounces to replay, one bit each.
+struct alignas(16) FilterCand {
+    unsigned long long mask;
+    uint32_t slot;
+    uint32_t pad;
+};
+// filter_kernel's block (lanes = slots): each block compacts its candidates into its own stretch of the
+// list and leaves a 16-B head {candidate rays, candidate queries, queries of its other rays, 0}.
+constexpr uint32_t kFilterBlock = 1024;
+ARX_HOST_DEVICE inline uint64_t path_filter_heads(uint64_t n) { return (n + kFilterBlock - 1) / kFilterBlock; }
+ARX_HOST_DEVICE inline uint64_t path_filter_list_bytes(uint64_t n) {
+    return n * sizeof(FilterCand) + 16 * path_filter_heads(n);
+}
+struct FilterArgs {
+    const void* planes;    // the allocation above
+    FilterCand* list;      // the frame set's candidate list, n entries ...
+    void* heads;           // ... and behind it path_filter_heads(n) heads (uint4), every one written by every filtered frame
+    float grow;            // the receiver box's margin, metres (kFilterMargin plus the slab test's own slack)
+};
+// How far the filter grows the receiver's box: see filter_kernel.
+constexpr float kFilterMargin = 0.0078125f;    // 2^-7 m
+constexpr float kFilterEndSlack = 0.00390625f;  // 2^-8 m: the recording's bound on |stored end - ray's own hit point|, per axis
+
 // Rays of a launch of n dealt out statically (slots [0, n_static) of the direction buffer, one range
 // per wave); the other n * dyn_share / 256 form the pool (trace_kernel).  The kernel and the host's
 // ordering of the pool's slots (launch_order_pool) both take it from here.
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define ARX_HOST_DEVICE __host__ __device__
-#else
-#define ARX_HOST_DEVICE
-#endif
 ARX_HOST_DEVICE inline uint64_t pool_static_rays(uint64_t n, uint32_t dyn_share) {
     return n - ((n * (uint64_t)dyn_share) >> 8);
 }

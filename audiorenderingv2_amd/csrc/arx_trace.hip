@@ -883,7 +883,19 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
     float oix = 0.f, oiy = 0.f, oiz = 0.f;
     uint32_t m_slot = 0u, m_cost = 0u;  // MEASURE: the current ray's buffer slot and its steps so far
     int rec_root = 0;  // RECORD: where a query starts, the scene root's code (a leaf code in a tiny scene)
-    if constexpr (RECORD) rec_root = a.qnodes[0].c[0].code;
+    // RECORD: the filter's planes (null: records alone) and the current ray's flags so far
+    float4* f_seg = nullptr;
+    float4* f_state = nullptr;
+    unsigned short* f_meta = nullptr;
+    unsigned short f_flags = 0;
+    if constexpr (RECORD) {
+        rec_root = a.qnodes[0].c[0].code;
+        if (a.gstack) {
+            f_seg = reinterpret_cast<float4*>(a.gstack);
+            f_state = f_seg + path_filter_seg_rows(a.max_bounces) * n;
+            f_meta = reinterpret_cast<unsigned short*>(f_state + (uint64_t)a.max_bounces * n);
+        }
+    }
     while (true) {
 #if ARX_TRACE_PROF
         ++pf[10];
@@ -897,14 +909,41 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
 #endif
         if (active && (LEAN ? t.node == -1 : !trav)) {  // the query is done: shade it
             const uint32_t rx_before = n_rx;
+            int f_depth = 0;                            // RECORD with the filter's planes: the query's bounce ...
+            float3 f_q = make_float3(0.f, 0.f, 0.f);  // ... and the ray's own hit point, pos + t * dir
             if constexpr (RECORD) {
                 const uint64_t at = (uint64_t)s.depth * n + m_slot;
                 float4* rec_hit = reinterpret_cast<float4*>(a.rec);
                 float2* rec_bary = reinterpret_cast<float2*>(rec_hit + (uint64_t)a.max_bounces * n);
                 rec_hit[at] = make_float4(t.best.t, __int_as_float(t.best.id), __int_as_float(t.best.unit), t.best.v);
                 rec_bary[at] = make_float2(t.best.w, t.best.det);
+                if (f_seg) {  // what the query started from (arx_layout.hpp, the path filter)
+                    f_seg[at] = make_float4(s.pos.x, s.pos.y, s.pos.z, s.dist);
+                    f_state[at] = make_float4(s.dir.x, s.dir.y, s.dir.z, s.e);
+                    f_depth = s.depth;
+                    f_q = add3(s.pos, scale3(t.best.t, s.dir));
+                }
             }
             shade<!RECORD>(a, tbase, s, r, t.best, n_rx, n_miss);
+            if constexpr (RECORD) {
+                if (f_seg) {
+                    // filter_kernel's margin rests on this: every point of [pos, pos + t * dir] lies within
+                    // kFilterEndSlack per axis of the stored segment [pos, the pos shade() left].  A ray
+                    // that breaks it once (a grazing hit's t, a degenerate triangle's reflection, a NaN)
+                    // is replayed whole.
+                    if (t.best.unit >= 0) {
+                        const float3 dq = sub3(f_q, s.pos);
+                        const float dev = fmaxf(fmaxf(fabsf(dq.x), fabsf(dq.y)), fabsf(dq.z));
+                        if (!(dev <= kFilterEndSlack)) f_flags |= kFilterWild;
+                    }
+                    if (!wants_query(a, s)) {  // the ray's last query: the last segment's end and the per-ray record
+                        const uint32_t cnt = (uint32_t)f_depth + 1u;
+                        if (cnt <= a.max_bounces) f_seg[(uint64_t)cnt * n + m_slot] = make_float4(s.pos.x, s.pos.y, s.pos.z, s.dist);
+                        f_meta[m_slot] = (unsigned short)((cnt & kFilterCount) | f_flags | (t.best.unit < 0 ? kFilterMiss : 0) |
+                                                          (n_rx != rx_before ? kFilterMarked : 0));
+                    }
+                }
+            }
             if (!wants_query(a, s)) {
                 active = false;
                 // the ray retires.  One the receiver ended says nothing about its length once the
@@ -942,7 +981,11 @@ __global__ __launch_bounds__(BLOCK, MINW) void trace_kernel(TraceArgs a) {
                 if (i < w_end) {
                     ray_init(a, s, a.ray_begin + i);
                     active = wants_query(a, s);
-                    if constexpr (RECORD) m_slot = (uint32_t)i;
+                    if constexpr (RECORD) {
+                        m_slot = (uint32_t)i;
+                        f_flags = 0;
+                        if (f_seg && !active) f_meta[i] = 0;  // a ray that never queries
+                    }
                     if constexpr (MEASURE) {
                         m_slot = (uint32_t)i;  // i < n <= 2^31 - 1 rays
                         m_cost = 0u;
@@ -1160,6 +1203,273 @@ __global__ __launch_bounds__(BLOCK) void replay_kernel(TraceArgs a) {
             shade(a, tbase, s, r, t.best, n_rx, n_miss);
             active = wants_query(a, s);
         }
+    }
+    flush_counters(a, n_q, n_rx, n_miss, lane);
+}
+
+// ------------------------------------------------------- the path filter ---
+// A filtered replay: the recording also stored what every query started from (arx_layout.hpp), so the
+// queries of a ray no longer depend on each other, and a frame needs only those whose segment can
+// touch the receiver.  filter_kernel finds them, replay_cand_kernel runs them.
+//
+// filter_kernel, a lane per slot on a plain grid: the ray's rows of the segment plane, each read once
+// (the previous row stays in registers), segment [pos_b, pos_b+1] against the receiver's box, one bit
+// per bounce.  Always candidates: a last query that missed (its segment has no end) or that ended on a
+// receiver-marked triangle of the scene (its shading needs a.center), and every query of a ray the
+// recording flagged (kFilterWild).  No atomic anywhere: a block compacts its candidate rays into its own
+// stretch of the frame set's list and leaves a 16-B head -- how many, their candidate queries, and the
+// summed query counts of its rays without a candidate, which replay_cand_kernel adds to the frame's counters.
+//
+// The box is the f32 box of the top node's receiver child (cnodes[0], written by the receiver refit on
+// the same stream, so it follows the listener with no host copy), grown by a.grow on every side.  Why
+// that is enough -- the one place where exactness is argued and not inherited:
+//   - The traced frame ends a ray on the receiver in query b only if take_hit accepted a receiver
+//     triangle at some t <= best.t, best.t being the scene-only hit the record holds: the point
+//     X = pos_b + t * dir_b of the segment [pos_b, Q], Q = pos_b + best.t * dir_b.
+//   - X lies in that triangle up to the triangle test's rounding: t is the barycentric mean of the
+//     vertices' depths along the ray's major axis, so X is off the triangle by a few ulps of the
+//     coordinates' magnitude M times at most sqrt(3) (the major axis holds >= 1/sqrt(3) of |dir|),
+//     far below 1e-5 * M; and the triangle lies inside the box, which the refit pads by 1e-5 * M.
+//   - The stored segment ends at E = P + 1e-3 * dir', not at Q.  The recording checked, for this very
+//     query, |Q - E| <= kFilterEndSlack = 2^-8 m on every axis (else the ray is kFilterWild) -- no bound on
+//     |dir| or on how well t and the barycentric P agree is assumed.  X = pos_b + u (Q - pos_b), u in
+//     [0, 1], so the stored segment's point pos_b + u (E - pos_b) is within 2^-8 m of X per axis.
+//   - So a box grown by 2^-8 m plus the rounding above is met by the stored segment whenever the
+//     receiver can be hit.  kFilterMargin is 2^-7 m: twice that; the box is about 2 m wide, the slack costs nothing.
+//   - The slab test's own rounding: u = (plane - p) * rcp(d) carries a relative error below 2^-21
+//     (two subtractions, a 1-ulp reciprocal, a product), which is the exact u of a plane moved by
+//     |plane - p| * 2^-21 <= 2^-20 * M.  The host adds 2^-18 * M to a.grow, M from the grid that holds
+//     the scene, the emitter and the receiver.  A NaN anywhere compares as "candidate".
+__device__ __forceinline__ bool segment_meets_box(float4 p, float4 q, const float (&lo)[3], const float (&hi)[3]) {
+    const float pp[3] = {p.x, p.y, p.z}, qq[3] = {q.x, q.y, q.z};
+    float un = 0.0f, uf = 1.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float d = qq[k] - pp[k];
+        if (fabsf(d) < 1e-20f) d = (d < 0.0f) ? -1e-20f : 1e-20f;
+        const float inv = __builtin_amdgcn_rcpf(d);
+        const float u0 = (lo[k] - pp[k]) * inv, u1 = (hi[k] - pp[k]) * inv;
+        un = fmaxf(un, fminf(u0, u1));
+        uf = fminf(uf, fmaxf(u0, u1));
+    }
+    return !(un > uf);
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void filter_kernel(TraceArgs a, FilterArgs f) {
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool have = gid < n;
+    const uint64_t slot = have ? gid : n - 1;  // n >= 1 (launch_path_replay_filtered); idle lanes read in bounds
+    const float4* __restrict__ seg = reinterpret_cast<const float4*>(f.planes);
+    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(
+        seg + (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+    // the receiver's box: the same address for every lane, so scalar loads, once per wave
+    const BvhNode& top = a.cnodes[0];
+    const float lo[3] = {top.b[0] - f.grow, top.b[2] - f.grow, top.c[2] - f.grow};
+    const float hi[3] = {top.b[1] + f.grow, top.b[3] + f.grow, top.c[3] + f.grow};
+    const uint32_t m = have ? meta[slot] : 0u;
+    const uint32_t count = min(m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
+    uint32_t cmax = count;  // the wave's longest ray bounds the loop: every lane's loads stay unconditional
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, off, 64));
+    cmax = __builtin_amdgcn_readfirstlane(cmax);
+    unsigned long long mask = 0ull;
+    float4 p = seg[slot];
+#pragma unroll 4
+    for (uint32_t b = 0; b < cmax; ++b) {
+        // rows past the ray's last are not its own: it re-reads its last row (count <= max_bounces exists)
+        const float4 q = seg[(uint64_t)min(b + 1u, count) * n + slot];
+        const bool hit = segment_meets_box(p, q, lo, hi);
+        mask |= (hit && b < count) ? (1ull << b) : 0ull;
+        p = q;
+    }
+    if (count > 0u) {
+        const unsigned long long last = 1ull << (count - 1u), all = last | (last - 1ull);
+        if (m & (kFilterMiss | kFilterMarked)) mask |= last;
+        if (m & kFilterWild) mask = all;
+    }
+    // Output, with no atomic anywhere.  (One atomic per wave on a list cursor and the counters, 15 625 waves
+    // at C3 on two cache lines, was what bound this kernel: 0.26 ms for a 41 us read,
+    // profiles/r11/ab_path_filter.txt.)  The block compacts its candidates into its own stretch of the
+    // list, [blockIdx * BLOCK, ...): at most one entry per slot, so the stretch is the block's slots.  Its
+    // head holds how many, their queries, and the queries of the rays that need no replay, which
+    // replay_cand_kernel adds to the frame's counters with its own.
+    const bool cand = mask != 0ull;
+    const unsigned long long ballot = __ballot(cand);
+    constexpr int WAVES = BLOCK / 64;
+    __shared__ uint32_t w_cand[WAVES], w_cq[WAVES], w_nq[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned int cq = cand ? (unsigned int)__popcll(mask) : 0u, nq = cand ? 0u : count;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cq += __shfl_xor(cq, off, 64);
+        nq += __shfl_xor(nq, off, 64);
+    }
+    if (lane == 0) {
+        w_cand[wave] = (uint32_t)__popcll(ballot);
+        w_cq[wave] = cq;
+        w_nq[wave] = nq;
+    }
+    __syncthreads();
+    uint32_t before = 0u, t_cand = 0u, t_cq = 0u, t_nq = 0u;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        before += w < wave ? w_cand[w] : 0u;
+        t_cand += w_cand[w];
+        t_cq += w_cq[w];
+        t_nq += w_nq[w];
+    }
+    if (cand) {
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+        FilterCand c;
+        c.mask = mask;
+        c.slot = (uint32_t)slot;
+        c.pad = 0u;
+        // before + rank < the block's candidates <= its slots below n, so inside the list's n entries
+        f.list[(uint64_t)blockIdx.x * BLOCK + before + rank] = c;
+    }
+    // (a missed last query is always a candidate: no misses among the rays counted here)
+    if (threadIdx.x == 0) reinterpret_cast<uint4*>(f.heads)[blockIdx.x] = make_uint4(t_cand, t_cq, t_nq, 0u);
+}
+
+// replay_cand_kernel: a 64-lane block per 64 entries of each filter block's stretch of the list; the
+// stretch's head says how many it holds (device memory: nothing waits on the host), a lane per
+// candidate ray.  For each set bit, ascending: the stored
+// state and the cached hit, then replay_kernel's query -- setup_ray, the step on the top node with the
+// scene's child off, the receiver sub-tree -- on the same bits with the same functions.  If the receiver
+// gave the closest hit, or this is the ray's flagged last query, shade() runs and the ray ends; else
+// nothing is shaded, the next query's state being stored already.  A ray that does not end here ran its
+// recorded count of queries.  The queries of the rays filter_kernel retired come in through the heads.
+__global__ __launch_bounds__(64) void replay_cand_kernel(TraceArgs a, FilterArgs f) {
+    constexpr int BLOCK = 64;
+    // Block (fb, c) takes candidates [64 c, 64 c + 64) of filter block fb's stretch, so a stretch full of
+    // candidates is sixteen waves' work, not one wave's sixteen rounds: the pool's slots are ordered
+    // longest first with the rays the receiver ended in front (launch_order_pool), so the candidates
+    // crowd into a few stretches, and a wave per stretch took 0.93 ms at C3 where this takes 0.20.  Most
+    // blocks read their head and leave, before anything else is set up; a stretch's first block stays
+    // to add the head's query count.
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint32_t chunks = kFilterBlock / BLOCK;
+    const uint64_t fblocks = (n + kFilterBlock - 1) / kFilterBlock;
+    const uint64_t fb = blockIdx.x / chunks;
+    const uint32_t base = (blockIdx.x % chunks) * BLOCK;
+    if (fb >= fblocks) return;
+    const uint4 head = reinterpret_cast<const uint4*>(f.heads)[fb];  // the same address for every lane
+    const uint32_t n_cand = min(head.x, kFilterBlock);
+    if (base > 0u && base >= n_cand) return;
+    __shared__ int stk_lds[(kLdsStack + 1) * BLOCK];
+    __shared__ uint4 ncache[kNodeCache > 0 ? 2 * kNodeCache : 1];
+    if constexpr (kNodeCache > 0) {
+        const uint4* q = reinterpret_cast<const uint4*>(a.qnodes);
+        for (int i = threadIdx.x; i < 2 * kNodeCache; i += BLOCK) ncache[i] = q[i];
+        __syncthreads();
+    }
+    using Stack = LdsStack<BLOCK, kLdsStack>;
+    const int lane = threadIdx.x;
+    Stack stk;
+    stk.base = stk_lds + lane;
+    stk_lds[lane] = -1;
+    const __amdgpu_buffer_rsrc_t nrs = buffer_rsrc(a.qnodes, ARX_TRACE_IDXEN ? (short)sizeof(QNode2) : (short)0);
+    arx_i32x4 qrs;
+    {
+        const unsigned long long qa = (unsigned long long)a.qnodes;
+        qrs.x = (int)(uint32_t)qa;
+        qrs.y = (int)((qa >> 32) & 0xffffu);
+        qrs.z = 0x7fffffff;
+        qrs.w = 0x00020000;
+    }
+    const float4* tbase = reinterpret_cast<const float4*>(a.tris);
+    const __amdgpu_buffer_rsrc_t trs = buffer_rsrc(tbase);
+    const float4* __restrict__ rec_hit = reinterpret_cast<const float4*>(a.rec);
+    const float2* __restrict__ rec_bary = reinterpret_cast<const float2*>(rec_hit + (uint64_t)a.max_bounces * n);
+    const float4* __restrict__ seg = reinterpret_cast<const float4*>(f.planes);
+    const float4* __restrict__ state = seg + path_filter_seg_rows(a.max_bounces) * n;
+    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(state + (uint64_t)a.max_bounces * n);
+    uint32_t n_q = 0, n_rx = 0, n_miss = 0;
+    Ray r;
+    Trav t;
+    {
+        if (base == 0u && lane == 0) n_q += head.z;
+        const uint64_t i = fb * kFilterBlock + base + lane;
+        const bool have = base + lane < n_cand && i < n;
+        unsigned long long mask = 0ull;
+        uint64_t slot = 0;
+        uint32_t m = 0u;
+        if (have) {
+            const FilterCand c = f.list[i];
+            mask = c.mask;
+            slot = c.slot < n ? c.slot : n - 1;
+            m = meta[slot];
+        }
+        const uint32_t count = min(m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
+        mask &= count > 0u ? ((1ull << (count - 1u)) << 1) - 1ull : 0ull;  // bits of queries the ray ran
+        bool active = mask != 0ull, ended = false;
+        while (__ballot(active) != 0ull) {
+            float oix = 0.f, oiy = 0.f, oiz = 0.f;
+            t.node = -1;
+            t.sp = 0;
+            RayState s;
+            s.depth = -1;
+            int unit0 = -1;
+            if (active) {
+                const uint32_t b = (uint32_t)__builtin_ctzll(mask);
+                mask &= mask - 1ull;
+                const uint64_t at = (uint64_t)b * n + slot;
+                const float4 sp = seg[at], sd = state[at];
+                const float4 h = rec_hit[at];
+                const float2 hb = rec_bary[at];
+                s.pos = make_float3(sp.x, sp.y, sp.z);
+                s.dist = sp.w;
+                s.dir = make_float3(sd.x, sd.y, sd.z);
+                s.e = sd.w;
+                s.depth = (int)b;
+                t.best.t = h.x;
+                t.best.id = __float_as_int(h.y);
+                t.best.unit = __float_as_int(h.z);
+                t.best.v = h.w;
+                t.best.w = hb.x;
+                t.best.det = hb.y;
+                unit0 = t.best.unit;
+                setup_ray(r, s.pos, s.dir);
+                oix = (r.o[0] - a.qgrid.origin[0]) * r.inv[0];
+                oiy = (r.o[1] - a.qgrid.origin[1]) * r.inv[1];
+                oiz = (r.o[2] - a.qgrid.origin[2]) * r.inv[2];
+                r.inv[0] *= a.qgrid.scale[0];
+                r.inv[1] *= a.qgrid.scale[1];
+                r.inv[2] *= a.qgrid.scale[2];
+#if ARX_TRACE_SIGNSEL && ARX_TRACE_BITFLOAT
+                oix = __builtin_fmaf(8388608.0f, r.inv[0], oix);
+                oiy = __builtin_fmaf(8388608.0f, r.inv[1], oiy);
+                oiz = __builtin_fmaf(8388608.0f, r.inv[2], oiz);
+#endif
+                t.node = 0;
+                node_step<kFmtQ16, Stack, false, true>(r, oix, oiy, oiz, t, stk, nrs, ncache, qrs);
+            }
+            while (true) {
+                const unsigned long long m_node = __ballot(t.node >= 0);
+                const unsigned long long m_leaf = __ballot(t.node <= -2);
+                if ((m_node | m_leaf) == 0ull) break;
+                if (m_node != 0ull) {
+                    if (t.node >= 0) node_step<kFmtQ16, Stack, false>(r, oix, oiy, oiz, t, stk, nrs, ncache, qrs);
+                } else {
+                    leaf_step<kFmtQ16>(trs, r, t, stk);
+                }
+            }
+            if (active) {
+                const bool flagged = (uint32_t)s.depth + 1u == count && (m & (kFilterMiss | kFilterMarked)) != 0u;
+                if (t.best.unit != unit0 || flagged) {
+                    n_q += (uint32_t)s.depth + 1u;
+                    shade(a, tbase, s, r, t.best, n_rx, n_miss);
+                    ended = true;
+                    active = false;
+                } else if (mask == 0ull) {
+                    active = false;
+                }
+            }
+        }
+        if (have && !ended) n_q += count;
     }
     flush_counters(a, n_q, n_rx, n_miss, lane);
 }
@@ -1485,6 +1795,26 @@ hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s) {
     constexpr int RB = ARX_REPLAY_BLOCK;
     const uint64_t n_rays = a.ray_end - a.ray_begin;
     hipLaunchKernelGGL(replay_kernel<RB>, dim3((unsigned)((n_rays + RB - 1) / RB)), dim3(RB), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.hist || !a.counters || !a.rec || !a.cnodes || !f.planes ||
+        !f.list || !f.heads || a.max_bounces < 1 || a.max_bounces > kFilterMaxBounces)
+        return hipErrorInvalidValue;
+    if (a.clear_bins > 0 || a.clear_counters > 0) {
+        const hipError_t e = launch_clear(a.hist, a.clear_bins, a.counters, a.clear_counters, s);
+        if (e != hipSuccess) return e;
+    }
+    constexpr int FB = (int)kFilterBlock;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    const uint64_t fblocks = (n_rays + FB - 1) / FB;
+    // a wave per 64 entries of every filter block's stretch of the list
+    const uint64_t g2 = fblocks * (FB / 64);
+    if (g2 > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_kernel<FB>, dim3((unsigned)fblocks), dim3(FB), 0, s, a, f);
+    hipLaunchKernelGGL(replay_cand_kernel, dim3((unsigned)g2), dim3(64), 0, s, a, f);
     return hipGetLastError();
 }
 

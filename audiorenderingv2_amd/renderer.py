@@ -236,6 +236,20 @@ class AudioRenderer:
         check(lib().arx_debug_path_cache_state(self.handle, C.byref(st), C.byref(nb), C.byref(nq) if queries else None))
         return {"state": self.PATH_CACHE_STATES[st.value], "bytes": int(nb.value), "queries_recorded": int(nq.value)}
 
+    def set_path_filter(self, on: bool) -> None:
+        """arx_debug_set_path_filter: on (default) a replayed frame runs only the queries whose segment
+        crosses the receiver's box; off, every cached query as before."""
+        check(lib().arx_debug_set_path_filter(self.handle, 1 if on else 0))
+
+    def path_filter_state(self, candidates: bool = False) -> dict:
+        """arx_debug_path_filter_state: whether the last trace launch was a filtered replay, the bytes held
+        for the filter and, when asked for (synchronises), its candidate rays and queries."""
+        fl, nb, cr, cq = C.c_int32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().arx_debug_path_filter_state(self.handle, C.byref(fl), C.byref(nb),
+                                                C.byref(cr) if candidates else None, C.byref(cq) if candidates else None))
+        return {"filtered": bool(fl.value), "bytes": int(nb.value), "candidate_rays": int(cr.value),
+                "candidate_queries": int(cq.value)}
+
     def ray_order_buffer(self, count: int) -> dict:
         """arx_debug_ray_order_buffer: the first count slots (count x 4 floats) of the current frame
         set's direction buffer, the ray id of slot 0, the leading slots still in ray order and whether

@@ -608,6 +608,36 @@ arx_status arx_debug_path_cache_state(arx_renderer* r, int32_t* state, uint64_t*
 /* Host only: bytes of records for n_rays x max_bounces queries. */
 uint64_t arx_debug_path_cache_bytes(uint64_t n_rays, uint32_t max_bounces);
 
+/* The path filter: a replayed frame runs only the queries whose segment crosses the receiver's box.
+ *
+ * Nothing a query starts from (position, direction, energy, distance so far) depends on the listener
+ * either, so with the filter on (the default) the recording launch stores that as well: 32 B per query
+ * and 16 + 2 B per ray beside the 24-B records.  A replayed frame is then two launches.  The first reads
+ * each ray's stored positions once (16 B per query) and tests every segment against the receiver's
+ * box, grown by 2^-7 m plus rounding slack, as the receiver refit left it on the device.  A ray none of
+ * whose segments meets the box adds its recorded query count and is done; the others -- with every
+ * ray whose last query missed or ended on a receiver-marked triangle of the scene -- are listed, and
+ * the second launch replays their candidate queries alone, each from its stored state with the
+ * unfiltered replay's functions on the same bits.  Results are bit for bit the unfiltered replay's.
+ *
+ * This memory is OUTSIDE arx_debug_set_path_cache's max_bytes, which keeps counting the 24-B records
+ * alone: rays x (32 x max_bounces + 18) B of planes per renderer, plus 16 x rays B of candidate list
+ * and 16 B per 1024 rays of list heads per frame set that replays (at 1M rays x 16 bounces: 530 MB of planes and 16 MB per list,
+ * so 546 MB with one frame in flight and 562 MB with two).
+ * If it does not fit on the device the launch records and replays unfiltered, and that size is not
+ * tried again until the filter is switched off and on.  Also unfiltered, exactly as before: launches
+ * with max_bounces > 64, and frames whose emitter lies inside the receiver's grown box (every ray
+ * would be a candidate).  Switching the filter on over records made without state forgets them: the
+ * key's next launch records again, once (state "recorded"); switching it off keeps them. */
+arx_status arx_debug_set_path_filter(arx_renderer* r, int32_t on);
+/* Whether the last trace launch was a filtered replay, the bytes held for the filter (planes and
+ * lists), and that launch's candidate rays and candidate queries (0 unless filtered; synchronises
+ * when either is asked for).  Any output may be NULL. */
+arx_status arx_debug_path_filter_state(arx_renderer* r, int32_t* filtered, uint64_t* bytes, uint64_t* candidate_rays,
+                                       uint64_t* candidate_queries);
+/* Host only: bytes of the filter's planes for n_rays x max_bounces queries plus n_lists candidate lists. */
+uint64_t arx_debug_path_filter_bytes(uint64_t n_rays, uint32_t max_bounces, uint32_t n_lists);
+
 /* Debug / parity hooks. */
 arx_status arx_debug_ray_directions(uint64_t seed, uint64_t first_ray, uint64_t count, float* h_out_xyz,
                                     int device);
