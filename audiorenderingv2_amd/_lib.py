@@ -60,6 +60,21 @@ class ArxAcoustics(C.Structure):
     ]
 
 
+class ArxListenerPose(C.Structure):
+    """arx_listener_pose (16 B)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("yaw_deg", C.c_float)]
+
+
+class ArxListenerResult(C.Structure):
+    """arx_listener_result (48 B, no implicit padding)."""
+    _fields_ = [
+        ("queries", C.c_uint64), ("receiver_hits", C.c_uint64), ("misses", C.c_uint64),
+        ("candidate_rays", C.c_uint64), ("route", C.c_int32), ("reserved", C.c_int32), ("reserved2", C.c_uint64),
+    ]
+
+
+LISTENER_BATCHED, LISTENER_SINGLE = 0, 1  # ARX_LISTENER_*
+
 # include/arx.h ARX_ACOUSTICS_C* (the level tests' f64 literals) and ARX_VALID_* (bit order)
 ACOUSTICS_LEVELS = {5: 3.1622776601683794e-01, 10: 1.0000000000000001e-01, 25: 3.1622776601683794e-03,
                     35: 3.1622776601683794e-04}
@@ -157,6 +172,11 @@ SIGNATURES = {
     "arx_debug_path_filter_state": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                               C.POINTER(C.c_uint64)]),
     "arx_debug_path_filter_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "arx_render_listeners": (C.c_int, [_P, C.POINTER(ArxListenerPose), C.c_size_t, _P, _P, C.POINTER(ArxAcoustics),
+                                       C.POINTER(ArxListenerResult), _D]),
+    "arx_debug_set_listener_chunk": (C.c_int, [_P, C.c_int32]),
+    "arx_debug_listener_bytes": (C.c_uint64, [C.c_uint64, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
+    "arx_debug_listener_layout": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _I64]),
     "arx_debug_set_trace_path": (C.c_int, [_P, C.c_int]),
     "arx_debug_set_refit_pad": (C.c_int, [_P, C.c_float]),
     "arx_debug_check_tree_limits": (C.c_int, [C.c_uint64, C.c_uint64]),

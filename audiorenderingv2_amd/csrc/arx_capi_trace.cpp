@@ -581,7 +581,9 @@ arx_status arx::set_scene_image(arx_renderer* r, SceneRef img) {
     return ARX_OK;
 }
 
-arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end, bool timed, bool clear) {
+arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end, bool timed, bool clear,
+                           ReplayProbe* probe) {
+    if (probe) probe->ready = false;
     if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
     if (ray_end < ray_begin) return fail(ARX_ERR_INVALID_ARGUMENT, "ray_end < ray_begin");
     // global ray ids index the launch of N = x*y*z rays: energies are normalised by N and the
@@ -634,6 +636,7 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
         a.clear_counters = kCounters;
     }
     if (ray_end == ray_begin) {  // nothing to trace: the clear alone
+        if (probe) return ARX_OK;
         if (clear) ARX_HIP(launch_clear(r->hist(), 2 * (uint64_t)r->ir_len, f.d_counters, (int)kCounters, r->stream));
         return ARX_OK;
     }
@@ -730,7 +733,7 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     r->stats.trace_vgprs = r->occ[fmt][inst][0];
     r->stats.trace_waves_per_simd = r->occ[fmt][inst][1];
     r->stats.trace_waves_target = r->occ[fmt][inst][2];
-    if (timed && (st = r->trace_ring.begin(r->stream)) != ARX_OK) return st;
+    if (timed && !probe && (st = r->trace_ring.begin(r->stream)) != ARX_OK) return st;
     // Frames in flight: a ray-pool launch is sized for half the CUs' wave slots, so the next frame's
     // launch runs beside it for its whole length instead of only in its tail.  A launch of 1M rays
     // gives each lane about three rays; the last of them leave the lanes idle one by one, and a wave
@@ -751,6 +754,10 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     // measure), records the scene-only hits and replays them; the launches of that key after it only
     // replay.  Everything else is traced as above and costs what it did.
     PathCache& pc = r->path_cache;
+    // a probe decides what this launch would do and leaves what the last launch did as it was
+    const OrderKey probe_last_key = pc.last_key;
+    const bool probe_last_valid = pc.last_valid, probe_last_filtered = pc.last_filtered;
+    const int32_t probe_state = pc.state;
     pc.last_filtered = false;
     const bool cacheable = pc.mode == 1 && r->stream == f.stream && trace_can_cache(a, r->force_global_stack);
     bool replay = false, record = false;
@@ -793,7 +800,7 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
         } else if (final_dirs && repeated) {
             record = replay = true;
         }
-        if (record) {
+        if (record && !probe) {
             bool fits = true;
             if ((st = path_cache_reserve(r, n_launch, need, &fits)) != ARX_OK) return st;
             if (fits) {
@@ -804,6 +811,18 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
                 pc.no_room = need;  // not tried again per frame (arx_debug_set_path_cache forgets it)
             }
         }
+    }
+    if (probe) {
+        probe->ready = replay && !record && pc.filter_on && pc.has_state && pc.d_filter && pc.rec_stream == r->stream;
+        probe->args = a;
+        probe->args.dirs = pc.d_dirs;
+        probe->args.rec = pc.d_hits;
+        probe->planes = pc.d_filter;
+        pc.last_key = probe_last_key;
+        pc.last_valid = probe_last_valid;
+        pc.last_filtered = probe_last_filtered;
+        pc.state = probe_state;
+        return ARX_OK;
     }
     if (replay) {
         TraceArgs pa = a;
@@ -885,7 +904,521 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     return fif_done_traced(r);
 }
 
+// ---- a batch of listeners (arx_render_listeners) ----------------------------------------------------
+namespace {
+
+constexpr uint64_t kListenerCounterWords = 16;  // a listener's block: kCounters counters, its candidate tally, padding
+
+// arx_debug_listener_bytes' per-listener terms (include/arx.h)
+uint64_t listener_bytes_each(uint64_t n, int32_t ir_len, int64_t recv_nodes, int64_t recv_tris) {
+    return (uint64_t)recv_nodes * (sizeof(BvhNode) + sizeof(QNode2)) + (uint64_t)recv_tris * sizeof(TriRec) +
+           (sizeof(BvhNode) + sizeof(QNode2)) + sizeof(ListenerEntry) + 16ull * (uint64_t)ir_len +
+           kListenerCounterWords * 8 + 3 * sizeof(arx_acoustics) + 8ull * (uint64_t)ir_len + path_filter_list_bytes(n) +
+           4 * listener_work_words(n);
+}
+
+// One chunk's scratch (ListenerBatch::d_scratch): byte offsets, every region 16-B aligned.
+struct ListenerScratch {
+    uint64_t lists, list_stride, work, work_stride, table, hist, counters, res, ir, edc, acou, total;
+};
+ListenerScratch listener_scratch(uint64_t n, int32_t ir_len, int32_t chunk) {
+    ListenerScratch s;
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 15) & ~15ull;
+        return o;
+    };
+    const uint64_t J = (uint64_t)chunk;
+    s.list_stride = path_filter_list_bytes(n);
+    s.lists = take(J * s.list_stride);
+    s.work_stride = 4 * listener_work_words(n);
+    s.work = take(J * s.work_stride);
+    s.table = take(J * sizeof(ListenerEntry));
+    s.hist = take(J * 16 * (uint64_t)ir_len);
+    s.counters = take(J * kListenerCounterWords * 8);
+    s.res = take(J * 3 * sizeof(arx_acoustics));
+    s.ir = take(J * 8 * (uint64_t)ir_len);  // the chunk's left IRs, then its right IRs
+    s.edc = take(24 * (uint64_t)ir_len);
+    s.acou = take(acoustics_scratch_bytes());
+    s.total = at;
+    return s;
+}
+
+// The pinned block of a call of n listeners: table entries by batched order; counter blocks and results by
+// batched order in [0, n) and by pose index in [n, 2n) for the poses that went the one-listener route; the
+// tree's off-grid flag as the chunks left it.
+struct ListenerPinned {
+    ListenerEntry* entries;
+    unsigned long long* counters;
+    arx_acoustics* res;
+    unsigned int* flag;
+};
+size_t listener_pinned_bytes(size_t n) {
+    return n * sizeof(ListenerEntry) + 2 * n * kListenerCounterWords * 8 + 2 * n * 3 * sizeof(arx_acoustics) + 16;
+}
+ListenerPinned listener_pinned(void* base, size_t n) {
+    ListenerPinned p;
+    char* c = static_cast<char*>(base);
+    p.entries = reinterpret_cast<ListenerEntry*>(c);
+    c += n * sizeof(ListenerEntry);
+    p.counters = reinterpret_cast<unsigned long long*>(c);
+    c += 2 * n * kListenerCounterWords * 8;
+    p.res = reinterpret_cast<arx_acoustics*>(c);
+    c += 2 * n * 3 * sizeof(arx_acoustics);
+    p.flag = reinterpret_cast<unsigned int*>(c);
+    return p;
+}
+
+// The node and triangle arrays widened to hold a chunk's slots: new buffers, what the old ones held copied
+// on the device.  False: no room (the error cleared; the arrays as they were).
+bool widen_tree_arrays(arx_renderer* r, size_t need_nodes, size_t need_tris) {
+    if (need_nodes <= r->nodes_cap && need_tris <= r->tris_cap) return true;
+    if (sync_renderer(r) != ARX_OK) return false;
+    if (need_nodes > r->nodes_cap) {
+        BvhNode* cn = nullptr;
+        QNode2* qn = nullptr;
+        const size_t cap = need_nodes + 1024;
+        if (hipMalloc(&cn, cap * sizeof(BvhNode)) != hipSuccess || hipMalloc(&qn, cap * sizeof(QNode2)) != hipSuccess ||
+            hipMemcpy(cn, r->d_cnodes, r->nodes_cap * sizeof(BvhNode), hipMemcpyDeviceToDevice) != hipSuccess ||
+            hipMemcpy(qn, r->d_qnodes, r->nodes_cap * sizeof(QNode2), hipMemcpyDeviceToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(cn);
+            hipFree(qn);
+            return false;
+        }
+        hipFree(r->d_cnodes);
+        hipFree(r->d_qnodes);
+        r->d_cnodes = cn;
+        r->d_qnodes = qn;
+        r->nodes_cap = cap;
+    }
+    if (need_tris > r->tris_cap) {
+        TriRec* tr = nullptr;
+        const size_t cap = need_tris + 4096;
+        if (hipMalloc(&tr, cap * sizeof(TriRec)) != hipSuccess ||
+            hipMemcpy(tr, r->d_tris, r->tris_cap * sizeof(TriRec), hipMemcpyDeviceToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(tr);
+            return false;
+        }
+        hipFree(r->d_tris);
+        r->d_tris = tr;
+        r->tris_cap = cap;
+    }
+    return true;
+}
+
+// The chunk scratch for `chunk` listeners of n rays; false: no room (that size is not tried again).
+bool listener_scratch_reserve(arx_renderer* r, uint64_t n, int32_t chunk) {
+    ListenerBatch& lb = r->listeners;
+    if (lb.d_scratch && lb.rays == n && lb.ir_len == r->ir_len && lb.chunk >= chunk) return true;
+    const uint64_t need = listener_scratch(n, r->ir_len, chunk).total;
+    if (lb.no_room > 0 && need >= lb.no_room) return false;
+    if (sync_renderer(r) != ARX_OK) return false;
+    hipFree(lb.d_scratch);
+    lb.d_scratch = nullptr;
+    lb.scratch_bytes = 0;
+    lb.chunk = 0;
+    if (hipMalloc(&lb.d_scratch, need) != hipSuccess) {
+        (void)hipGetLastError();
+        lb.d_scratch = nullptr;
+        lb.no_room = need;
+        return false;
+    }
+    lb.scratch_bytes = need;
+    lb.chunk = chunk;
+    lb.rays = n;
+    lb.ir_len = r->ir_len;
+    return true;
+}
+
+// The grid grown once for a batch, as ensure_device_scene's `grow` branch grows it for a walking listener:
+// the new grid spans the old one, the scene, the emitter and [ulo, uhi] with half the extent as margin, the
+// top node and the scene are re-quantized on the device, and the renderer's own receiver is refit for it
+// by the next ensure_device_scene.
+arx_status grow_grid_for(arx_renderer* r, const float ulo[3], const float uhi[3]) {
+    const BvhBuild& sc = r->scene_img->bvh;
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = std::min(r->emitter[k], ulo[k]);
+        hi[k] = std::max(r->emitter[k], uhi[k]);
+        if (sc.root.count >= 0) {
+            lo[k] = std::min(lo[k], sc.root.lo[k]);
+            hi[k] = std::max(hi[k], sc.root.hi[k]);
+        }
+        lo[k] = std::min(lo[k], r->qgrid.origin[k]);
+        hi[k] = std::max(hi[k], r->qgrid.origin[k] + 65000.0f * r->qgrid.scale[k]);
+    }
+    ++r->tree_gen;
+    r->qgrid = make_qgrid(lo, hi, 0.5);
+    ARX_HIP(launch_requant16(r->d_cnodes, 1 + sc.nodes.size(), r->qgrid, r->d_qnodes, r->d_tree_flag, r->tree_gen, r->stream));
+    ++r->requants;
+    r->recv_pose_dirty = true;
+    return ARX_OK;
+}
+
+struct ListenerOut {
+    float* ir_left;
+    float* ir_right;
+    arx_acoustics* acoustics;
+    arx_listener_result* results;
+};
+
+arx_status render_listeners(arx_renderer* r, const arx_listener_pose* poses, size_t n, const ListenerOut& out,
+                            const ListenerPinned& pin) {
+    ListenerBatch& lb = r->listeners;
+    const uint64_t N = n_rays(r->cfg);
+    const size_t ir_len = (size_t)r->ir_len;
+    const bool analyse = out.acoustics != nullptr;
+    std::vector<int32_t> route(n, ARX_LISTENER_SINGLE);
+    std::vector<size_t> where(n, 0);  // the listener's block in pin.counters / pin.res
+    arx_status st;
+    // The one-listener route: the loop's own step, then its outputs queued on the stream.
+    auto single = [&](size_t j) -> arx_status {
+        const arx_listener_pose& p = poses[j];
+        arx_status s1 = arx_set_listener(r, p.x, p.y, p.z, p.yaw_deg);
+        if (s1 == ARX_OK) s1 = arx_render(r, nullptr);
+        if (s1 == ARX_OK && analyse && !r->cur().acou.queued) s1 = arx_analyze_ir(r);
+        if (s1 != ARX_OK) return s1;
+        const arx_renderer::FrameSet& f = r->cur();
+        where[j] = n + j;
+        if (out.ir_left) {
+            ARX_HIP(hipMemcpyAsync(out.ir_left + j * ir_len, f.d_ir, ir_len * sizeof(float), hipMemcpyDefault, r->stream));
+            ARX_HIP(hipMemcpyAsync(out.ir_right + j * ir_len, f.d_ir + ir_len, ir_len * sizeof(float), hipMemcpyDefault,
+                                   r->stream));
+        }
+        unsigned long long* hc = pin.counters + where[j] * kListenerCounterWords;
+        hc[kCounters] = 0;
+        ARX_HIP(hipMemcpyAsync(hc, f.d_counters, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, r->stream));
+        if (analyse)
+            ARX_HIP(hipMemcpyAsync(pin.res + 3 * where[j], f.acou.d_res, 3 * sizeof(arx_acoustics), hipMemcpyDeviceToHost,
+                                   r->stream));
+        route[j] = ARX_LISTENER_SINGLE;
+        return ARX_OK;
+    };
+    // 1. the warm-up: the next pose through arx_render proper until the key is recorded with its filter state
+    size_t first = 0;
+    ReplayProbe probe;
+    for (; first < n; ++first) {
+        if ((st = trace_rays(r, 0, N, false, false, &probe)) != ARX_OK) return st;
+        const bool can = probe.ready && r->recv_refit && !r->recv.tris.empty() && !r->use_w4 && N > 0 &&
+                         r->cfg.max_bounces <= kFilterMaxBounces;
+        if (can) break;
+        if ((st = single(first)) != ARX_OK) return st;
+    }
+    // 2. the batched poses: grid, slots and scratch before the first launch; any "no" sends the rest through the loop
+    std::vector<size_t> batched;
+    bool batch = first < n;
+    if (batch) {
+        // the union of the remaining poses' receiver bounds on the grid (grown once if need be)
+        const float keep[4] = {r->center[0], r->center[1], r->center[2], r->yaw};
+        float ulo[3] = {1e30f, 1e30f, 1e30f}, uhi[3] = {-1e30f, -1e30f, -1e30f};
+        for (size_t j = first; j < n; ++j) {
+            r->center[0] = poses[j].x; r->center[1] = poses[j].y; r->center[2] = poses[j].z;
+            float lo[3], hi[3];
+            bool empty = false;
+            receiver_bound(r, lo, hi, &empty);
+            for (int k = 0; k < 3; ++k) {
+                ulo[k] = std::min(ulo[k], lo[k]);
+                uhi[k] = std::max(uhi[k], hi[k]);
+            }
+        }
+        for (int k = 0; k < 3; ++k) r->center[k] = keep[k];
+        if (!qgrid_contains(r->qgrid, ulo, uhi) && (st = grow_grid_for(r, ulo, uhi)) != ARX_OK) return st;
+    }
+    const int64_t recv_nodes = (int64_t)r->recv.nodes.size(), recv_tris = (int64_t)r->recv.tris.size();
+    const int64_t own_nodes = r->scene_img ? 1 + (int64_t)r->scene_img->bvh.nodes.size() + recv_nodes : 0;
+    const int64_t own_tris = r->scene_img ? (int64_t)r->scene_img->bvh.tris.size() + recv_tris : 0;
+    int32_t chunk = 0;
+    if (batch) {
+        const uint64_t each = listener_bytes_each(N, r->ir_len, recv_nodes, recv_tris);
+        chunk = lb.forced_chunk > 0 ? lb.forced_chunk : (int32_t)std::min<uint64_t>(kListenerChunkMax, kListenerBudget / each);
+        chunk = (int32_t)std::min<size_t>((size_t)chunk, n - first);
+        batch = chunk >= 1;
+    }
+    if (batch) {
+        // the extended tree must pass the kernels' offset limits and the structural check, slot by slot
+        const ListenerLayout last = listener_layout(own_nodes, own_tris, recv_nodes, recv_tris, chunk, chunk - 1, trace_node_cache());
+        batch = check_buffer_offsets((size_t)last.total_nodes, (size_t)last.total_tris) == ARX_OK;
+        std::vector<BvhNode> moved(r->recv.nodes);
+        for (int32_t s = 0; batch && s < chunk; s += std::max(1, chunk - 1)) {  // the first and the last slot
+            const ListenerLayout l = listener_layout(own_nodes, own_tris, recv_nodes, recv_tris, chunk, s, trace_node_cache());
+            const int32_t ns = (int32_t)(l.node_begin - (own_nodes - recv_nodes)), ts = (int32_t)(l.tri_begin - (own_tris - recv_tris));
+            for (size_t i = 0; i < moved.size(); ++i)
+                for (int c = 0; c < 2; ++c) {
+                    const int32_t cnt = r->recv.nodes[i].d[2 + c];
+                    moved[i].d[c] = r->recv.nodes[i].d[c] + (cnt == 0 ? ns : cnt > 0 ? ts : 0);
+                }
+            const char* why = "";
+            batch = validate_bvh_range(moved.data(), (size_t)l.node_begin, moved.size(), (size_t)last.total_nodes,
+                                       (size_t)last.total_tris, &why);
+        }
+        batch = batch && widen_tree_arrays(r, (size_t)last.total_nodes, (size_t)last.total_tris) &&
+                listener_scratch_reserve(r, N, chunk);
+        chunk = std::min(chunk, std::max(lb.chunk, 0));
+    }
+    if (batch) {
+        // the arrays may have moved and the grid grown: the replay's arguments as they stand now
+        if ((st = trace_rays(r, 0, N, false, false, &probe)) != ARX_OK) return st;
+        batch = probe.ready && chunk >= 1;
+    }
+    const ListenerScratch sc = listener_scratch(lb.rays, lb.ir_len, std::max(lb.chunk, 1));
+    char* const d_base = static_cast<char*>(lb.d_scratch);
+    const float fgrow = batch ? path_filter_grow(probe.args.qgrid) : 0.0f;
+    if (batch) {
+        // which poses are batched: not those whose box holds the emitter (every ray a candidate), nor one off the grid
+        const float keep[4] = {r->center[0], r->center[1], r->center[2], r->yaw};
+        for (size_t j = first; j < n; ++j) {
+            r->center[0] = poses[j].x; r->center[1] = poses[j].y; r->center[2] = poses[j].z;
+            float lo[3], hi[3];
+            bool empty = false;
+            receiver_bound(r, lo, hi, &empty);
+            bool inside = !empty;
+            for (int k = 0; k < 3; ++k)
+                inside = inside && r->emitter[k] >= lo[k] - 2.0f * fgrow && r->emitter[k] <= hi[k] + 2.0f * fgrow;
+            if (inside || !qgrid_contains(r->qgrid, lo, hi)) continue;
+            const size_t b = batched.size();
+            const int32_t slot = (int32_t)(b % (size_t)chunk);
+            const ListenerLayout l = listener_layout(own_nodes, own_tris, recv_nodes, recv_tris, chunk, slot, trace_node_cache());
+            ListenerEntry& e = pin.entries[b];
+            std::memset(&e, 0, sizeof(e));
+            for (int k = 0; k < 3; ++k) e.center[k] = r->center[k];
+            e.top = (int32_t)l.top;
+            receiver_rotation(poses[j].yaw_deg, e.m);
+            e.pad = r->debug_refit_pad > 0.0f ? r->debug_refit_pad : refit_pad(r);
+            e.node_shift = (int32_t)(l.node_begin - (own_nodes - recv_nodes));
+            e.tri_shift = (int32_t)(l.tri_begin - (own_tris - recv_tris));
+            e.hist = reinterpret_cast<unsigned long long*>(d_base + sc.hist) + (size_t)slot * 2 * ir_len;
+            e.counters = reinterpret_cast<unsigned long long*>(d_base + sc.counters) + (size_t)slot * kListenerCounterWords;
+            e.cand = e.counters + kCounters;
+            e.list = reinterpret_cast<FilterCand*>(d_base + sc.lists + (uint64_t)slot * sc.list_stride);
+            e.heads = e.list + N;
+            e.work = reinterpret_cast<unsigned int*>(d_base + sc.work + (uint64_t)slot * sc.work_stride);
+            where[j] = b;
+            route[j] = ARX_LISTENER_BATCHED;
+            batched.push_back(j);
+        }
+        for (int k = 0; k < 3; ++k) r->center[k] = keep[k];
+        r->yaw = keep[3];
+    }
+    // 3. the poses that take the one-listener route in place; the call's last pose waits, so that its frame is the last
+    for (size_t j = first; j + 1 < n; ++j)
+        if (route[j] == ARX_LISTENER_SINGLE && (st = single(j)) != ARX_OK) return st;
+    // 4. the chunks, all on the one stream
+    const float e0 = initial_energy(r->cfg);
+    const double unit = std::ldexp((double)e0, -arx_frac_bits(N));
+    for (size_t c0 = 0; c0 < batched.size(); c0 += (size_t)chunk) {
+        const int32_t J = (int32_t)std::min<size_t>((size_t)chunk, batched.size() - c0);
+        ListenerEntry* d_table = reinterpret_cast<ListenerEntry*>(d_base + sc.table);
+        unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(d_base + sc.hist);
+        unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(d_base + sc.counters);
+        arx_acoustics* d_res = reinterpret_cast<arx_acoustics*>(d_base + sc.res);
+        float* d_irl = reinterpret_cast<float*>(d_base + sc.ir);
+        float* d_irr = d_irl + (size_t)lb.chunk * ir_len;
+        ARX_HIP(hipMemcpyAsync(d_table, pin.entries + c0, (size_t)J * sizeof(ListenerEntry), hipMemcpyHostToDevice, r->stream));
+        ARX_HIP(launch_clear(d_hist, (uint64_t)J * 2 * ir_len, d_cnt, (int)(J * kListenerCounterWords), r->stream));
+        RefitArgs ra;
+        std::memset(&ra, 0, sizeof(ra));
+        ra.local_tris = r->d_recv_local;
+        ra.n_tris = (int32_t)recv_tris;
+        ra.tri_base = (int32_t)(own_tris - recv_tris);
+        ra.local_nodes = r->d_recv_nodes;
+        ra.n_nodes = (int32_t)recv_nodes;
+        ra.node_base = (int32_t)(own_nodes - recv_nodes);
+        ra.level_nodes = r->d_recv_levels;
+        ra.level_start = r->d_recv_levels + r->recv_level_count;
+        ra.n_levels = r->recv_levels;
+        ra.root_ref = r->recv.root.ref;
+        ra.root_count = r->recv.root.count;
+        ra.grid = r->qgrid;
+        ra.tris = r->d_tris;
+        ra.cnodes = r->d_cnodes;
+        ra.qnodes = r->d_qnodes;
+        ra.flag = r->d_tree_flag;
+        ra.flag_value = r->tree_gen;
+        ARX_HIP(launch_receiver_refit_multi(ra, d_table, J, r->stream));
+        FilterArgs fa;
+        fa.planes = probe.planes;
+        fa.list = nullptr;  // per listener, from the table
+        fa.heads = nullptr;
+        fa.grow = fgrow;
+        ARX_HIP(launch_listeners_replay(probe.args, fa, d_table, J, r->stream));
+        for (int32_t i = 0; i < J; ++i) {
+            const size_t j = batched[c0 + (size_t)i];
+            const long long* h = reinterpret_cast<const long long*>(d_hist + (size_t)i * 2 * ir_len);
+            float* il = d_irl + (size_t)i * ir_len;
+            float* irr = d_irr + (size_t)i * ir_len;
+            ARX_HIP(launch_finalize_ir(h, il, irr, r->ir_len, unit, r->cfg.is_mono, r->stream));
+            ++r->ir_generation;
+            if (analyse) {
+                AcousticsArgs args{};
+                args.hist = h;
+                args.n = r->ir_len;
+                args.sample_rate = r->cfg.sample_rate;
+                args.unit = unit;
+                args.edc = reinterpret_cast<long long*>(d_base + sc.edc);
+                args.out = d_res + 3 * i;
+                args.scratch = d_base + sc.acou;
+                args.shape = r->scan_shape == 0 ? kScanDefault : r->scan_shape;
+                ARX_HIP(launch_acoustics(args, r->stream));
+            }
+            if (out.ir_left) {
+                ARX_HIP(hipMemcpyAsync(out.ir_left + j * ir_len, il, ir_len * sizeof(float), hipMemcpyDefault, r->stream));
+                ARX_HIP(hipMemcpyAsync(out.ir_right + j * ir_len, irr, ir_len * sizeof(float), hipMemcpyDefault, r->stream));
+            }
+        }
+        ARX_HIP(hipMemcpyAsync(pin.counters + c0 * kListenerCounterWords, d_cnt, (size_t)J * kListenerCounterWords * 8,
+                               hipMemcpyDeviceToHost, r->stream));
+        if (analyse)
+            ARX_HIP(hipMemcpyAsync(pin.res + 3 * c0, d_res, (size_t)J * 3 * sizeof(arx_acoustics), hipMemcpyDeviceToHost, r->stream));
+        ARX_HIP(hipMemcpyAsync(pin.flag, r->d_tree_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, r->stream));
+        pin.flag[1] = r->tree_gen;
+        // the call's last pose is the renderer's last frame: histogram, counters, IR, candidate list, analysis
+        if (batched.back() == n - 1 && c0 + (size_t)J == batched.size()) {
+            const int32_t i = J - 1;
+            if ((st = begin_frame(r)) != ARX_OK) return st;
+            arx_renderer::FrameSet& f = r->cur();
+            ARX_HIP(hipMemcpyAsync(f.d_hist, d_hist + (size_t)i * 2 * ir_len, 2 * ir_len * sizeof(unsigned long long),
+                                   hipMemcpyDeviceToDevice, r->stream));
+            ARX_HIP(hipMemcpyAsync(f.d_counters, d_cnt + (size_t)i * kListenerCounterWords, kCounters * sizeof(unsigned long long),
+                                   hipMemcpyDeviceToDevice, r->stream));
+            ARX_HIP(hipMemcpyAsync(f.d_ir, d_irl + (size_t)i * ir_len, ir_len * sizeof(float), hipMemcpyDeviceToDevice, r->stream));
+            ARX_HIP(hipMemcpyAsync(f.d_ir + ir_len, d_irr + (size_t)i * ir_len, ir_len * sizeof(float), hipMemcpyDeviceToDevice,
+                                   r->stream));
+            PathCache& pc = r->path_cache;
+            pc.state = kPathReplayed;
+            pc.last_key = pc.key;
+            pc.last_valid = true;
+            pc.last_filtered = false;
+            if (path_filter_list_reserve(r, N)) {
+                ARX_HIP(hipMemcpyAsync(f.d_filter_list, d_base + sc.lists + (uint64_t)i * sc.list_stride, N * sizeof(FilterCand),
+                                       hipMemcpyDeviceToDevice, r->stream));
+                ARX_HIP(hipMemcpyAsync(static_cast<FilterCand*>(f.d_filter_list) + f.filter_list_cap,
+                                       d_base + sc.lists + (uint64_t)i * sc.list_stride + N * sizeof(FilterCand),
+                                       16 * path_filter_heads(N), hipMemcpyDeviceToDevice, r->stream));
+                pc.last_filtered = true;
+                pc.filter_slot = r->slot;
+                pc.filter_rays = N;
+            }
+            r->conv_ir_dirty = true;
+            r->conv_live_ir_dirty = true;
+            const arx_listener_pose& p = poses[n - 1];
+            r->center[0] = p.x; r->center[1] = p.y; r->center[2] = p.z;
+            r->yaw = p.yaw_deg;
+            if ((analyse || r->auto_analyze) && (st = arx_analyze_ir(r)) != ARX_OK) return st;
+        }
+    }
+    if (n >= 1 && first < n && route[n - 1] == ARX_LISTENER_SINGLE && (st = single(n - 1)) != ARX_OK) return st;
+    // 5. the one synchronisation, then the host-side outputs
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    if (!batched.empty() && pin.flag[1] != 0 && pin.flag[0] == pin.flag[1])
+        return fail(ARX_ERR_INTERNAL, "receiver refit / re-quantization: a box left the quantization grid");
+    for (size_t j = 0; j < n; ++j) {
+        const unsigned long long* hc = pin.counters + where[j] * kListenerCounterWords;
+        if (out.results) {
+            arx_listener_result& o = out.results[j];
+            std::memset(&o, 0, sizeof(o));
+            o.queries = hc[0];
+            o.receiver_hits = hc[1];
+            o.misses = hc[2];
+            o.candidate_rays = route[j] == ARX_LISTENER_BATCHED ? hc[kCounters] : 0;
+            o.route = route[j];
+        }
+        if (analyse) std::memcpy(out.acoustics + 3 * j, pin.res + 3 * where[j], 3 * sizeof(arx_acoustics));
+    }
+    return ARX_OK;
+}
+
+}  // namespace
+
+void arx::free_listener_batch(ListenerBatch& b) {
+    hipFree(b.d_scratch);
+    if (b.h_pinned) hipHostFree(b.h_pinned);
+    if (b.ev0) hipEventDestroy(b.ev0);
+    if (b.ev1) hipEventDestroy(b.ev1);
+    const int32_t forced = b.forced_chunk;
+    b = ListenerBatch{};
+    b.forced_chunk = forced;
+}
+
 extern "C" {
+
+arx_status arx_render_listeners(arx_renderer* r, const arx_listener_pose* poses, size_t n, float* ir_left, float* ir_right,
+                                arx_acoustics* acoustics, arx_listener_result* results, double* ms) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    if (n == 0) return ARX_OK;
+    if (!poses) return fail(ARX_ERR_INVALID_ARGUMENT, "poses is NULL");
+    if ((ir_left == nullptr) != (ir_right == nullptr))
+        return fail(ARX_ERR_INVALID_ARGUMENT, "ir_left and ir_right: both or neither");
+    for (size_t j = 0; j < n; ++j)
+        if (!std::isfinite(poses[j].x) || !std::isfinite(poses[j].y) || !std::isfinite(poses[j].z) ||
+            !std::isfinite(poses[j].yaw_deg))
+            return fail(ARX_ERR_INVALID_ARGUMENT, "pose %zu is not finite", j);
+    if (r->fif != 1) return fail(ARX_ERR_INVALID_ARGUMENT, "a batch of listeners needs one frame in flight");
+    if (r->stream != r->cur().stream) return fail(ARX_ERR_INVALID_ARGUMENT, "a batch of listeners needs the renderer's own stream");
+    if (r->d_hist_ext) return fail(ARX_ERR_INVALID_ARGUMENT, "a batch of listeners needs the renderer's own histogram");
+    if (!r->scene_img) return fail(ARX_ERR_NOT_READY, "arx_set_scene has not been called");
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    ListenerBatch& lb = r->listeners;
+    if (n > lb.h_listeners) {  // nothing of an earlier call is in flight: every call ends synchronised
+        if (lb.h_pinned) hipHostFree(lb.h_pinned);
+        lb.h_pinned = nullptr;
+        lb.h_listeners = 0;
+        ARX_HIP(hipHostMalloc(&lb.h_pinned, listener_pinned_bytes(n), hipHostMallocDefault));
+        lb.h_listeners = n;
+    }
+    const ListenerPinned pin = listener_pinned(lb.h_pinned, n);
+    pin.flag[0] = pin.flag[1] = 0u;
+    const bool timed = r->timing || ms != nullptr;
+    if (timed) {
+        if (!lb.ev0) ARX_HIP(hipEventCreate(&lb.ev0));
+        if (!lb.ev1) ARX_HIP(hipEventCreate(&lb.ev1));
+        ARX_HIP(hipEventRecord(lb.ev0, r->stream));
+    }
+    const float saved[4] = {r->center[0], r->center[1], r->center[2], r->yaw};
+    const ListenerOut out{ir_left, ir_right, acoustics, results};
+    arx_status st = render_listeners(r, poses, n, out, pin);
+    arx_set_listener(r, saved[0], saved[1], saved[2], saved[3]);  // the listener set before the call, refit by the next frame
+    if (st != ARX_OK) return st;
+    if (timed) {
+        ARX_HIP(hipEventRecord(lb.ev1, r->stream));
+        ARX_HIP(hipEventSynchronize(lb.ev1));
+        float t = 0.0f;
+        ARX_HIP(hipEventElapsedTime(&t, lb.ev0, lb.ev1));
+        if (ms) *ms = (double)t;
+    }
+    return ARX_OK;
+}
+
+arx_status arx_debug_set_listener_chunk(arx_renderer* r, int32_t listeners) {
+    if (!r || listeners < 0 || listeners > kListenerChunkMax)
+        return fail(ARX_ERR_INVALID_ARGUMENT, "listener chunk: 0 (automatic) or 1..%d", kListenerChunkMax);
+    r->listeners.forced_chunk = listeners;
+    return ARX_OK;
+}
+
+uint64_t arx_debug_listener_bytes(uint64_t n_rays, int32_t ir_len, int64_t recv_nodes, int64_t recv_tris, int32_t listeners) {
+    if (ir_len < 0 || recv_nodes < 0 || recv_tris < 0 || listeners < 0) return 0;
+    return (uint64_t)listeners * listener_bytes_each(n_rays, ir_len, recv_nodes, recv_tris);
+}
+
+arx_status arx_debug_listener_layout(int64_t n_scene_nodes, int64_t n_scene_tris, int64_t recv_nodes, int64_t recv_tris,
+                                     int32_t listeners, int32_t slot, int64_t out5[5]) {
+    if (!out5 || n_scene_nodes < 0 || n_scene_tris < 0 || recv_nodes < 0 || recv_tris < 0 || listeners < 1 ||
+        listeners > kListenerChunkMax || slot < 0 || slot >= listeners)
+        return fail(ARX_ERR_INVALID_ARGUMENT, "bad listener layout arguments");
+    const ListenerLayout l = listener_layout(1 + n_scene_nodes + recv_nodes, n_scene_tris + recv_tris, recv_nodes, recv_tris,
+                                             listeners, slot, trace_node_cache());
+    const arx_status fit = check_buffer_offsets((size_t)l.total_nodes, (size_t)l.total_tris);
+    if (fit != ARX_OK) return fit;
+    out5[0] = l.node_begin;
+    out5[1] = l.node_begin + recv_nodes;
+    out5[2] = l.tri_begin;
+    out5[3] = l.tri_begin + recv_tris;
+    out5[4] = l.top;
+    return ARX_OK;
+}
 
 arx_status arx_set_scene(arx_renderer* r, const float* tri_v, const float* tri_abs, int64_t n) {
     if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");

@@ -152,6 +152,33 @@ struct PathCache {
 };
 void free_path_cache(PathCache& p);
 
+// A batch of listeners (arx_render_listeners, include/arx.h): the scratch of one chunk -- per listener a
+// candidate list with its heads, a table entry, a histogram, a counter block, a candidate tally, three
+// analysis results and an f32 IR pair; then one decay-curve buffer and the analysis kernels' scratch --
+// in one allocation made by the first batched call, kept across calls and freed when it must grow and at
+// arx_destroy; outside the path cache's cap.  The chunk's receiver slots live in the renderer's node and
+// triangle arrays (listener_layout, arx_layout.hpp), which the first batched call widens.
+struct ListenerBatch {
+    int32_t forced_chunk = 0;     // arx_debug_set_listener_chunk: 0 automatic
+    void* d_scratch = nullptr;
+    uint64_t scratch_bytes = 0;
+    int32_t chunk = 0;            // listeners the scratch was laid out for ...
+    uint64_t rays = 0;            // ... at this many rays ...
+    int32_t ir_len = 0;           // ... and this IR length
+    uint64_t no_room = 0;         // > 0: a scratch of this size did not fit on the device: not tried again
+    void* h_pinned = nullptr;     // per listener of a call: its table entry, counters, tally and results
+    size_t h_listeners = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+};
+constexpr uint64_t kListenerBudget = 512ull << 20;  // scratch of an automatic chunk
+void free_listener_batch(ListenerBatch& b);
+// What a replayed, filtered frame of the current key would launch, as trace_rays decides it (probe below).
+struct ReplayProbe {
+    bool ready = false;  // the key is recorded with its filter state, and this launch would only replay
+    TraceArgs args;      // the replay's arguments (dirs and rec the cache's)
+    const void* planes = nullptr;
+};
+
 // A ring of (start, end) event pairs around the last kTraceRing timed launches of one kind.  A launch
 // that is not timed records nothing and does not advance the ring.
 constexpr int kTraceRing = 256;
@@ -171,7 +198,10 @@ struct EventRing {
 // arx_trace_rays with the per-launch events recorded or not (arx_set_timing, or a caller asking for the
 // time); clear: the direction pre-pass zeroes the histogram and counters first (render() after
 // begin_frame, instead of arx_clear_histogram's launch)
-arx_status trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end, bool timed, bool clear = false);
+// probe: nothing is launched; the scene is brought up to date, the path cache's decision for this launch
+// is made as usual, and *probe says whether it is "replay, with filter state".
+arx_status trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end, bool timed, bool clear = false,
+                      ReplayProbe* probe = nullptr);
 // arx_clear_histogram without its launch: with frames in flight, the next frame takes the next set
 arx_status begin_frame(arx_renderer* r);
 // Install a built scene (arx_set_scene's second half): uploaded at the next trace.
@@ -249,6 +279,7 @@ struct arx_renderer {
     int32_t ray_order = ARX_RAY_ORDER_DEFAULT;  // arx_debug_set_ray_order: 0 identity, directions kept; 1 longest-first pool; 2 directions re-made per launch
     uint64_t scene_gen = 0;        // scenes installed (set_scene_image): part of a frame set's OrderKey
     arx::PathCache path_cache;     // scene-only hits of the last repeated key (arx_debug_set_path_cache)
+    arx::ListenerBatch listeners;  // arx_render_listeners' chunk scratch
     arx::QGrid qgrid{};
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)

@@ -44,6 +44,15 @@ hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s);
 // every slot, replay_cand_kernel over the candidates it listed.  max_bounces in [1, kFilterMaxBounces];
 // f.list and f.heads belong to the frame set whose stream s is.  Results are launch_path_replay's.
 hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, hipStream_t s);
+// The filtered replay for a chunk of `listeners` table entries at once (filter_multi_kernel: one read of the
+// segment plane serves kListenerFilterWidth listeners; replay_cand_multi_kernel: one launch for the whole
+// chunk).  a is the replay's arguments (dirs and rec the cache's); its hist, counters and center and f's
+// list and heads are taken from each entry instead, the box from the entry's top node in a.cnodes.  Per
+// listener the results are launch_path_replay_filtered's.  No clear: the caller clears the chunk's block.
+hipError_t launch_listeners_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
+                                   int32_t listeners, hipStream_t s);
+// Nodes below this index are answered by the trace kernels' LDS copy (0: this build has none).
+int32_t trace_node_cache();
 // Lanes of the largest persistent trace grid (columns of the global traversal stack).
 inline uint64_t trace_max_lanes(int cus) { return (uint64_t)(cus > 0 ? cus : 256) * 2048ull; }
 // i64 histogram -> f32 IR (+ mono merge); unit = e0 * 2^-frac_bits.
@@ -116,6 +125,9 @@ struct RefitArgs {
 };
 size_t receiver_refit_lds(int32_t n_tris, int32_t n_nodes, int32_t n_levels);  // bytes of LDS
 hipError_t launch_receiver_refit(const RefitArgs& a, hipStream_t s);
+// A chunk of listeners (arx_render_listeners): block j refits the receiver at d_table[j]'s pose into that
+// entry's slot and writes its top node; a's own m / t / pad are not used, and there is no CW4 copy.
+hipError_t launch_receiver_refit_multi(const RefitArgs& a, const ListenerEntry* d_table, int32_t listeners, hipStream_t s);
 // The quantized copy of nodes [0, n) re-made on the device from the coded f32 nodes for grid g
 // (quantize_nodes16's arithmetic, bit for bit): a new scene or a grown grid costs one launch and
 // no host work or upload.  *flag is raised to flag_value (atomic max) if a box falls off the grid.

@@ -208,6 +208,51 @@ struct FilterArgs {
 constexpr float kFilterMargin = 0.0078125f;    // 2^-7 m
 constexpr float kFilterEndSlack = 0.00390625f;  // 2^-8 m: the recording's bound on |stored end - ray's own hit point|, per axis
 
+// A batch of listeners (arx_render_listeners; filter_multi_kernel / replay_cand_multi_kernel, arx_trace.hip,
+// and the receiver refit's chunk launch, arx_receiver.hip).  A chunk of J listeners is answered from one
+// recording at once: each listener j has a slot -- a placed copy of the receiver sub-tree and a top node of
+// its own -- in the node and triangle arrays behind the renderer's own receiver range, and an entry of
+// this table in device memory.  Everything a kernel takes from an entry is the same for a whole wave
+// (a block works for one listener), so it stays in scalar registers.
+struct alignas(16) ListenerEntry {
+    float center[3];                // the listener's position: shade()'s a.center and the refit's translation
+    int32_t top;                    // its top node: child 0 empty, child 1 the slot's receiver root
+    float m[9];                     // the refit's rotation (RefitArgs::m)
+    float pad;                      // the refit's box padding (RefitArgs::pad)
+    int32_t node_shift;             // slot node index - the renderer's own receiver node index
+    int32_t tri_shift;              // the same for triangle records
+    unsigned long long* hist;       // [2*ir_len]
+    unsigned long long* counters;   // kCounters words of arx_internal.hpp: [0] queries [1] receiver hits [2] misses
+    FilterCand* list;               // n entries ...
+    void* heads;                    // ... and path_filter_heads(n) heads
+    unsigned long long* cand;       // one word: the candidate rays of the listener's frame (summed heads)
+    unsigned int* work;             // [0] the candidate launch's work items, from [4] the items: stretch * 16 + part
+};
+// words of a listener's work items for n rays: the count's 16 B, then a word per 64 entries of every stretch
+ARX_HOST_DEVICE inline uint64_t listener_work_words(uint64_t n) { return 4 + (kFilterBlock / 64) * path_filter_heads(n); }
+static_assert(sizeof(ListenerEntry) == 112, "ListenerEntry: arx_debug_listener_bytes counts 112 B");
+constexpr int32_t kListenerChunkMax = 64;   // listeners of one chunk (gridDim.y of the candidate launch)
+constexpr int32_t kListenerFilterWidth = 8; // listeners whose boxes one read of a segment is tested against
+// Where chunk slot `slot` of `listeners` lives, for a tree of own_nodes nodes (top node, scene, the
+// renderer's own receiver) and own_tris triangle records, a receiver of recv_nodes / recv_tris, and a
+// kernel whose LDS node cache answers for nodes below node_cache: the tops first, at or above the
+// cache, then the slots' nodes; the slots' triangles behind the renderer's own.
+struct ListenerLayout {
+    int64_t node_begin, tri_begin, top, total_nodes, total_tris;
+};
+ARX_HOST_DEVICE inline ListenerLayout listener_layout(int64_t own_nodes, int64_t own_tris, int64_t recv_nodes,
+                                                       int64_t recv_tris, int64_t listeners, int64_t slot,
+                                                       int64_t node_cache) {
+    const int64_t base = own_nodes > node_cache ? own_nodes : node_cache;
+    ListenerLayout l;
+    l.top = base + slot;
+    l.node_begin = base + listeners + slot * recv_nodes;
+    l.tri_begin = own_tris + slot * recv_tris;
+    l.total_nodes = base + listeners + listeners * recv_nodes;
+    l.total_tris = own_tris + listeners * recv_tris;
+    return l;
+}
+
 // Rays of a launch of n dealt out statically (slots [0, n_static) of the direction buffer, one range
 // per wave); the other n * dyn_share / 256 form the pool (trace_kernel).  The kernel and the host's
 // ordering of the pool's slots (launch_order_pool) both take it from here.

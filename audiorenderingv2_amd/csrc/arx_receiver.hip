@@ -75,7 +75,14 @@ __device__ __forceinline__ size_t refit_nd_offset(int32_t n_tris, int32_t n_node
     return ((size_t)9 * n_tris + (size_t)6 * n_nodes + 3) & ~(size_t)3;
 }
 
-__global__ __launch_bounds__(kRefitThreads) void receiver_refit_kernel(RefitArgs a) {
+// The refit of one placed receiver.  node_shift / tri_shift move everything it writes -- the triangle
+// records, the sub-tree's nodes, and the child codes and leaf offsets that name them -- from the
+// renderer's own receiver range (where local_nodes' references point) to a listener slot
+// (ListenerEntry, arx_layout.hpp); top is the top node whose receiver child it writes.  (0, 0, 0) is the
+// renderer's own receiver.  MULTI: a slot's top node also gets its empty child 0, and no CW4 copy.
+template <bool MULTI>
+__device__ __forceinline__ void refit_body(const RefitArgs& a, const int32_t node_shift, const int32_t tri_shift,
+                                           const int32_t top) {
     extern __shared__ float lds[];
     float* wv = lds;                   // world vertices, 9 per receiver triangle
     float* nb = lds + 9 * a.n_tris;    // node boxes (lo xyz, hi xyz), unpadded
@@ -140,7 +147,7 @@ __global__ __launch_bounds__(kRefitThreads) void receiver_refit_kernel(RefitArgs
             wv[9 * i + 3 * j + 1] = o[j][1];
             wv[9 * i + 3 * j + 2] = o[j][2];
         }
-        a.tris[a.tri_base + i] = dst;
+        a.tris[a.tri_base + tri_shift + i] = dst;
       }
     }
     __syncthreads();
@@ -177,7 +184,8 @@ __global__ __launch_bounds__(kRefitThreads) void receiver_refit_kernel(RefitArgs
                 const int32_t ref = sd[c], count = sd[2 + c];
                 float lo[3], hi[3];
                 child_box(ref, count, lo, hi);
-                write_child(a, inv, a.node_base + ln, c, lo, hi, child_code(ref, count), count < 0);
+                write_child(a, inv, a.node_base + node_shift + ln, c, lo, hi,
+                            child_code(ref + (count == 0 ? node_shift : tri_shift), count), count < 0);
                 for (int k = 0; k < 3; ++k) {
                     blo[k] = fminf(blo[k], lo[k]);
                     bhi[k] = fmaxf(bhi[k], hi[k]);
@@ -194,9 +202,11 @@ __global__ __launch_bounds__(kRefitThreads) void receiver_refit_kernel(RefitArgs
     if (threadIdx.x == 0) {
         float lo[3], hi[3];
         child_box(a.root_ref, a.root_count, lo, hi);
-        write_child(a, inv, 0, 1, lo, hi, child_code(a.root_ref, a.root_count), a.root_count < 0);
+        write_child(a, inv, top, 1, lo, hi, child_code(a.root_ref + (a.root_count == 0 ? node_shift : tri_shift), a.root_count),
+                    a.root_count < 0);
+        if constexpr (MULTI) write_child(a, inv, top, 0, lo, hi, kEmptyChildCode, true);
     }
-    if (!a.wbuf) return;
+    if (MULTI || !a.wbuf) return;
     // 4. the CW4 copy: every receiver CW4 node from the refit boxes of its BVH2 children (padded as
     //    the coded nodes), its leaf triangles, and the top node
     for (int i = threadIdx.x; i < a.n_w4; i += kRefitThreads) {
@@ -250,6 +260,20 @@ __global__ __launch_bounds__(kRefitThreads) void receiver_refit_kernel(RefitArgs
         a.wbuf[0] = make_uint4(q.w[0], q.w[1], q.w[2], q.w[3]);
         a.wbuf[1] = make_uint4(q.w[4], q.w[5], q.w[6], q.w[7]);
     }
+}
+
+__global__ __launch_bounds__(kRefitThreads) void receiver_refit_kernel(RefitArgs a) { refit_body<false>(a, 0, 0, 0); }
+
+// A chunk of listeners: block j places the receiver at table entry j's pose into that entry's slot.
+__global__ __launch_bounds__(kRefitThreads) void receiver_refit_multi_kernel(RefitArgs a,
+                                                                             const ListenerEntry* __restrict__ tbl) {
+    const ListenerEntry& e = tbl[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a.m[k] = e.m[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.t[k] = e.center[k];
+    a.pad = e.pad;
+    refit_body<true>(a, e.node_shift, e.tri_shift, e.top);
 }
 
 __global__ __launch_bounds__(256) void requant_w4_kernel(const W4NodeF* __restrict__ nodes, uint64_t n, QGrid g,
@@ -338,6 +362,14 @@ hipError_t launch_receiver_refit(const RefitArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(receiver_refit_kernel, dim3(1), dim3(kRefitThreads), receiver_refit_lds(a.n_tris, a.n_nodes, a.n_levels),
                        s,
                        a);
+    return hipGetLastError();
+}
+
+hipError_t launch_receiver_refit_multi(const RefitArgs& a, const ListenerEntry* d_table, int32_t listeners, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!d_table || listeners < 1 || listeners > kListenerChunkMax || a.n_tris < 1 || a.wbuf) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(receiver_refit_multi_kernel, dim3((unsigned)listeners), dim3(kRefitThreads),
+                       receiver_refit_lds(a.n_tris, a.n_nodes, a.n_levels), s, a, d_table);
     return hipGetLastError();
 }
 

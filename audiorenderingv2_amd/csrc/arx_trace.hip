@@ -1474,6 +1474,306 @@ __global__ __launch_bounds__(64) void replay_cand_kernel(TraceArgs a, FilterArgs
     flush_counters(a, n_q, n_rx, n_miss, lane);
 }
 
+// ------------------------------------------------- a batch of listeners ---
+// arx_render_listeners: many listeners answered from one recording.  Neither the records nor the filter's
+// planes depend on the listener, so a listener is a box to cull the stored segments against and a receiver
+// sub-tree to query; a chunk of them has its sub-trees placed side by side (ListenerEntry, arx_layout.hpp).
+//
+// filter_multi_kernel is filter_kernel with the segment in registers tested against F listeners' boxes:
+// one read of the segment plane serves F listeners (blockIdx.y picks the F).  Per listener the arithmetic,
+// the mask, the block's stretch of that listener's list and its head are filter_kernel's for that listener
+// alone: the box is the same six floats of the listener's top node with the same grow, segment_meets_box is
+// the same function, and the compaction runs per listener on its own ballot.  The boxes wait in LDS, six
+// floats a listener, read by every lane at the same address.
+template <int BLOCK, int F>
+__global__ __launch_bounds__(BLOCK) void filter_multi_kernel(TraceArgs a, FilterArgs f,
+                                                             const ListenerEntry* __restrict__ tbl, int32_t listeners) {
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool have = gid < n;
+    const uint64_t slot = have ? gid : n - 1;  // n >= 1 (launch_listeners_replay); idle lanes read in bounds
+    const float4* __restrict__ seg = reinterpret_cast<const float4*>(f.planes);
+    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(
+        seg + (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+    const int j0 = (int)blockIdx.y * F;  // this pass's listeners: [j0, min(j0 + F, listeners))
+    __shared__ float box[F][6];
+    if (threadIdx.x < F) {
+        const int i = threadIdx.x;
+        float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f};
+        if (j0 + i < listeners) {
+            const BvhNode& top = a.cnodes[tbl[j0 + i].top];  // child 1: the slot's receiver, as the refit left it
+            lo[0] = top.b[0] - f.grow; lo[1] = top.b[2] - f.grow; lo[2] = top.c[2] - f.grow;
+            hi[0] = top.b[1] + f.grow; hi[1] = top.b[3] + f.grow; hi[2] = top.c[3] + f.grow;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            box[i][k] = lo[k];
+            box[i][3 + k] = hi[k];
+        }
+    }
+    __syncthreads();
+    const uint32_t m = have ? meta[slot] : 0u;
+    const uint32_t count = min(m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
+    uint32_t cmax = count;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, off, 64));
+    cmax = __builtin_amdgcn_readfirstlane(cmax);
+    unsigned long long mask[F];
+#pragma unroll
+    for (int i = 0; i < F; ++i) mask[i] = 0ull;
+    float4 p = seg[slot];
+#pragma unroll 2
+    for (uint32_t b = 0; b < cmax; ++b) {
+        const float4 q = seg[(uint64_t)min(b + 1u, count) * n + slot];
+        const unsigned long long bit = b < count ? (1ull << b) : 0ull;
+#pragma unroll
+        for (int i = 0; i < F; ++i) {
+            const float lo[3] = {box[i][0], box[i][1], box[i][2]}, hi[3] = {box[i][3], box[i][4], box[i][5]};
+            mask[i] |= segment_meets_box(p, q, lo, hi) ? bit : 0ull;
+        }
+        p = q;
+    }
+    if (count > 0u) {
+        const unsigned long long last = 1ull << (count - 1u), all = last | (last - 1ull);
+#pragma unroll
+        for (int i = 0; i < F; ++i) {
+            if (m & (kFilterMiss | kFilterMarked)) mask[i] |= last;
+            if (m & kFilterWild) mask[i] = all;
+        }
+    }
+    // Output per listener as filter_kernel's: no atomic, the block's own stretch of the listener's list, a head.
+    constexpr int WAVES = BLOCK / 64;
+    __shared__ uint32_t w_cand[F][WAVES], w_cq[F][WAVES], w_nq[F][WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long ballot[F];
+#pragma unroll
+    for (int i = 0; i < F; ++i) {
+        const bool cand = mask[i] != 0ull;
+        ballot[i] = __ballot(cand);
+        unsigned int cq = cand ? (unsigned int)__popcll(mask[i]) : 0u, nq = cand ? 0u : count;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            cq += __shfl_xor(cq, off, 64);
+            nq += __shfl_xor(nq, off, 64);
+        }
+        if (lane == 0) {
+            w_cand[i][wave] = (uint32_t)__popcll(ballot[i]);
+            w_cq[i][wave] = cq;
+            w_nq[i][wave] = nq;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < F; ++i) {
+        if (j0 + i >= listeners) break;  // a ragged last pass (the same for the whole block)
+        const ListenerEntry& e = tbl[j0 + i];
+        uint32_t before = 0u, t_cand = 0u, t_cq = 0u, t_nq = 0u;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            before += w < wave ? w_cand[i][w] : 0u;
+            t_cand += w_cand[i][w];
+            t_cq += w_cq[i][w];
+            t_nq += w_nq[i][w];
+        }
+        if (mask[i] != 0ull) {
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot[i] >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)ballot[i], 0u));
+            FilterCand c;
+            c.mask = mask[i];
+            c.slot = (uint32_t)slot;
+            c.pad = 0u;
+            // before + rank < the block's candidates <= its slots below n, so inside the list's n entries
+            e.list[(uint64_t)blockIdx.x * BLOCK + before + rank] = c;
+        }
+        if (threadIdx.x == 0) reinterpret_cast<uint4*>(e.heads)[blockIdx.x] = make_uint4(t_cand, t_cq, t_nq, 0u);
+    }
+}
+
+// cand_work_kernel, a block per listener: the listener's work items in stretch order -- for every stretch
+// its first 64 entries (that item also adds the stretch's head) and every further 64 that hold a
+// candidate -- as (stretch * 16 + part) words behind their count (ListenerEntry::work).  replay_cand_kernel
+// launches a block for each of a frame's 16 x stretches parts and lets the empty ones leave; with a chunk
+// of listeners those are hundreds of thousands of blocks that only read a head, and dispatching them was
+// what the chunk's candidate launch took (profiles/r12/listeners_kernel_stats.csv).  No atomic: a block-wide
+// scan of the parts per stretch, tile after tile.
+__global__ __launch_bounds__(1024) void cand_work_kernel(const ListenerEntry* __restrict__ tbl, uint32_t fblocks) {
+    constexpr int BLOCK = 1024, WAVES = BLOCK / 64;
+    const ListenerEntry& e = tbl[blockIdx.x];
+    const uint4* __restrict__ heads = reinterpret_cast<const uint4*>(e.heads);
+    __shared__ uint32_t w_sum[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t done = 0u;  // items of the tiles before this one (the same in every thread)
+    for (uint32_t t0 = 0u; t0 < fblocks; t0 += BLOCK) {
+        const uint32_t fb = t0 + threadIdx.x;
+        uint32_t parts = 0u;
+        if (fb < fblocks) parts = max(1u, (min(heads[fb].x, kFilterBlock) + 63u) / 64u);
+        uint32_t incl = parts;  // inclusive scan within the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t v = (uint32_t)__shfl_up((int)incl, off, 64);
+            if (lane >= off) incl += v;
+        }
+        if (lane == 63) w_sum[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0u, total = 0u;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            before += w < wave ? w_sum[w] : 0u;
+            total += w_sum[w];
+        }
+        const uint32_t at = done + before + incl - parts;  // <= 16 * fb: inside the 16 * fblocks words
+        for (uint32_t c = 0u; c < parts; ++c) e.work[4u + at + c] = fb * 16u + c;
+        done += total;
+        __syncthreads();  // w_sum is written again by the next tile
+    }
+    if (threadIdx.x == 0) e.work[0] = done;
+}
+
+// replay_cand_multi_kernel is replay_cand_kernel with the listener taken from blockIdx.y: the histogram,
+// the counters, shade()'s centre, the list and the heads come from the listener's table entry (the same for
+// the whole block, so they stay scalar), and the query enters the listener's own top node instead of node 0
+// -- child 0 empty and skipped, child 1 the slot's receiver root -- so it is the same arithmetic on the same
+// boxes and triangles.  The per-ray chain, the functions and the order of set bits are replay_cand_kernel's.
+// What differs is which block takes which 64 entries: a listener's blocks walk its work items
+// (cand_work_kernel) gridDim.x apart, so neighbouring items -- the candidates crowd into few stretches --
+// go to different blocks, and no block is launched only to leave.  A stretch's first item also adds the
+// stretch's candidate rays to the listener's tally (e.cand).
+__global__ __launch_bounds__(64) void replay_cand_multi_kernel(TraceArgs a, FilterArgs f,
+                                                               const ListenerEntry* __restrict__ tbl) {
+    constexpr int BLOCK = 64;
+    const ListenerEntry& e = tbl[blockIdx.y];
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint64_t fblocks = (n + kFilterBlock - 1) / kFilterBlock;
+    const uint32_t n_items = min(e.work[0], (uint32_t)min(fblocks * (kFilterBlock / BLOCK), (uint64_t)0xffffffffu));
+    if (blockIdx.x >= n_items) return;
+    for (int k = 0; k < 3; ++k) a.center[k] = e.center[k];
+    a.hist = e.hist;
+    a.counters = e.counters;
+    f.list = e.list;
+    const int top = e.top;
+    __shared__ int stk_lds[(kLdsStack + 1) * BLOCK];
+    __shared__ uint4 ncache[kNodeCache > 0 ? 2 * kNodeCache : 1];
+    if constexpr (kNodeCache > 0) {
+        const uint4* q = reinterpret_cast<const uint4*>(a.qnodes);
+        for (int i = threadIdx.x; i < 2 * kNodeCache; i += BLOCK) ncache[i] = q[i];
+        __syncthreads();
+    }
+    using Stack = LdsStack<BLOCK, kLdsStack>;
+    const int lane = threadIdx.x;
+    Stack stk;
+    stk.base = stk_lds + lane;
+    stk_lds[lane] = -1;
+    const __amdgpu_buffer_rsrc_t nrs = buffer_rsrc(a.qnodes, ARX_TRACE_IDXEN ? (short)sizeof(QNode2) : (short)0);
+    arx_i32x4 qrs;
+    {
+        const unsigned long long qa = (unsigned long long)a.qnodes;
+        qrs.x = (int)(uint32_t)qa;
+        qrs.y = (int)((qa >> 32) & 0xffffu);
+        qrs.z = 0x7fffffff;
+        qrs.w = 0x00020000;
+    }
+    const float4* tbase = reinterpret_cast<const float4*>(a.tris);
+    const __amdgpu_buffer_rsrc_t trs = buffer_rsrc(tbase);
+    const float4* __restrict__ rec_hit = reinterpret_cast<const float4*>(a.rec);
+    const float2* __restrict__ rec_bary = reinterpret_cast<const float2*>(rec_hit + (uint64_t)a.max_bounces * n);
+    const float4* __restrict__ seg = reinterpret_cast<const float4*>(f.planes);
+    const float4* __restrict__ state = seg + path_filter_seg_rows(a.max_bounces) * n;
+    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(state + (uint64_t)a.max_bounces * n);
+    uint32_t n_q = 0, n_rx = 0, n_miss = 0;
+    Ray r;
+    Trav t;
+    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const uint32_t word = e.work[4u + item];  // the same address for every lane, like the head
+        const uint64_t fb = min((uint64_t)(word >> 4), fblocks - 1);
+        const uint32_t base = (word & 15u) * BLOCK;
+        const uint4 head = reinterpret_cast<const uint4*>(e.heads)[fb];
+        const uint32_t n_cand = min(head.x, kFilterBlock);
+        if (base == 0u && lane == 0) {
+            n_q += head.z;
+            if (head.x) atomicAdd(e.cand, (unsigned long long)head.x);
+        }
+        const uint64_t i = fb * kFilterBlock + base + lane;
+        const bool have = base + lane < n_cand && i < n;
+        unsigned long long mask = 0ull;
+        uint64_t slot = 0;
+        uint32_t m = 0u;
+        if (have) {
+            const FilterCand c = f.list[i];
+            mask = c.mask;
+            slot = c.slot < n ? c.slot : n - 1;
+            m = meta[slot];
+        }
+        const uint32_t count = min(m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
+        mask &= count > 0u ? ((1ull << (count - 1u)) << 1) - 1ull : 0ull;  // bits of queries the ray ran
+        bool active = mask != 0ull, ended = false;
+        while (__ballot(active) != 0ull) {
+            float oix = 0.f, oiy = 0.f, oiz = 0.f;
+            t.node = -1;
+            t.sp = 0;
+            RayState s;
+            s.depth = -1;
+            int unit0 = -1;
+            if (active) {
+                const uint32_t b = (uint32_t)__builtin_ctzll(mask);
+                mask &= mask - 1ull;
+                const uint64_t at = (uint64_t)b * n + slot;
+                const float4 sp = seg[at], sd = state[at];
+                const float4 h = rec_hit[at];
+                const float2 hb = rec_bary[at];
+                s.pos = make_float3(sp.x, sp.y, sp.z);
+                s.dist = sp.w;
+                s.dir = make_float3(sd.x, sd.y, sd.z);
+                s.e = sd.w;
+                s.depth = (int)b;
+                t.best.t = h.x;
+                t.best.id = __float_as_int(h.y);
+                t.best.unit = __float_as_int(h.z);
+                t.best.v = h.w;
+                t.best.w = hb.x;
+                t.best.det = hb.y;
+                unit0 = t.best.unit;
+                setup_ray(r, s.pos, s.dir);
+                oix = (r.o[0] - a.qgrid.origin[0]) * r.inv[0];
+                oiy = (r.o[1] - a.qgrid.origin[1]) * r.inv[1];
+                oiz = (r.o[2] - a.qgrid.origin[2]) * r.inv[2];
+                r.inv[0] *= a.qgrid.scale[0];
+                r.inv[1] *= a.qgrid.scale[1];
+                r.inv[2] *= a.qgrid.scale[2];
+#if ARX_TRACE_SIGNSEL && ARX_TRACE_BITFLOAT
+                oix = __builtin_fmaf(8388608.0f, r.inv[0], oix);
+                oiy = __builtin_fmaf(8388608.0f, r.inv[1], oiy);
+                oiz = __builtin_fmaf(8388608.0f, r.inv[2], oiz);
+#endif
+                t.node = top;  // the listener's top node, its empty child 0 off as the scene's is in node 0
+                node_step<kFmtQ16, Stack, false, true>(r, oix, oiy, oiz, t, stk, nrs, ncache, qrs);
+            }
+            while (true) {
+                const unsigned long long m_node = __ballot(t.node >= 0);
+                const unsigned long long m_leaf = __ballot(t.node <= -2);
+                if ((m_node | m_leaf) == 0ull) break;
+                if (m_node != 0ull) {
+                    if (t.node >= 0) node_step<kFmtQ16, Stack, false>(r, oix, oiy, oiz, t, stk, nrs, ncache, qrs);
+                } else {
+                    leaf_step<kFmtQ16>(trs, r, t, stk);
+                }
+            }
+            if (active) {
+                const bool flagged = (uint32_t)s.depth + 1u == count && (m & (kFilterMiss | kFilterMarked)) != 0u;
+                if (t.best.unit != unit0 || flagged) {
+                    n_q += (uint32_t)s.depth + 1u;
+                    shade(a, tbase, s, r, t.best, n_rx, n_miss);
+                    ended = true;
+                    active = false;
+                } else if (mask == 0ull) {
+                    active = false;
+                }
+            }
+        }
+        if (have && !ended) n_q += count;
+    }
+    flush_counters(a, n_q, n_rx, n_miss, lane);
+}
+
 __global__ void finalize_ir_kernel(const long long* __restrict__ hist, float* __restrict__ L, float* __restrict__ R,
                                    int32_t ir_len, double unit, int32_t mono) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1817,6 +2117,30 @@ hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, 
     hipLaunchKernelGGL(replay_cand_kernel, dim3((unsigned)g2), dim3(64), 0, s, a, f);
     return hipGetLastError();
 }
+
+hipError_t launch_listeners_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
+                                   int32_t listeners, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.rec || !a.cnodes || !f.planes || !d_table ||
+        listeners < 1 || listeners > kListenerChunkMax || a.max_bounces < 1 || a.max_bounces > kFilterMaxBounces ||
+        a.ray_end <= a.ray_begin)
+        return hipErrorInvalidValue;
+    constexpr int FB = (int)kFilterBlock;
+    constexpr int F = (int)kListenerFilterWidth;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    const uint64_t fblocks = (n_rays + FB - 1) / FB;
+    const uint64_t g2 = fblocks * (FB / 64);
+    if (g2 > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((filter_multi_kernel<FB, F>), dim3((unsigned)fblocks, (unsigned)((listeners + F - 1) / F)), dim3(FB), 0,
+                       s, a, f, d_table, listeners);
+    // the candidates: each listener's work items, then a fixed number of blocks that walk them
+    hipLaunchKernelGGL(cand_work_kernel, dim3((unsigned)listeners), dim3(1024), 0, s, d_table, (uint32_t)fblocks);
+    constexpr uint64_t kCandBlocks = 8192;  // of one wave each: what the device holds at once, and a half more
+    const uint64_t per = std::min<uint64_t>(g2, (kCandBlocks + (uint64_t)listeners - 1) / (uint64_t)listeners);
+    hipLaunchKernelGGL(replay_cand_multi_kernel, dim3((unsigned)per, (unsigned)listeners), dim3(64), 0, s, a, f, d_table);
+    return hipGetLastError();
+}
+int32_t trace_node_cache() { return kNodeCache; }
 
 hipError_t launch_order_pool(const void* dirs_in, void* dirs_out, const unsigned short* cost, uint32_t* bins, uint64_t n,
                              hipStream_t s) {

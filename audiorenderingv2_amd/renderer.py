@@ -18,7 +18,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import ACOUSTICS_VALID, ArxAcoustics, ArxConfig, ArxStats, check, fptr, lib
+from ._lib import ACOUSTICS_VALID, ArxAcoustics, ArxConfig, ArxListenerPose, ArxListenerResult, ArxStats, check, fptr, lib
 from .formats import write_float_lines
 from .scene import Scene
 
@@ -250,6 +250,39 @@ class AudioRenderer:
         return {"filtered": bool(fl.value), "bytes": int(nb.value), "candidate_rays": int(cr.value),
                 "candidate_queries": int(cq.value)}
 
+    def set_listener_chunk(self, n: int) -> None:
+        """arx_debug_set_listener_chunk: listeners per chunk of render_listeners (0: automatic, else 1..64)."""
+        check(lib().arx_debug_set_listener_chunk(self.handle, int(n)))
+
+    def render_listeners(self, poses, irs: bool | tuple = False, acoustics: bool = True) -> dict:
+        """arx_render_listeners: a batch of listeners (x, y, z, yaw_deg) rendered from one recorded path
+        set, bit for bit the loop of setSphereCenterInOptix + render (+ analyze_ir) over them; the
+        listener set before stays.  irs: False, True (host arrays) or a pair of DeviceBuffers / device
+        pointers of K * ir_len floats each (returned as given).  Returns {"ir": (L[K, ir_len],
+        R[K, ir_len]) | None, "acoustics": [{"left", "right", "sum"}] * K | None, "stats": a structured
+        array of arx_listener_result's fields, "ms": the call's device time}."""
+        P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 4))
+        k = P.shape[0]
+        n = self.ir_length
+        ir = None
+        pl = pr = None
+        if irs is True:
+            ir = (np.zeros((k, n), np.float32), np.zeros((k, n), np.float32))
+            pl, pr = ir[0].ctypes.data, ir[1].ctypes.data
+        elif irs:
+            ir = tuple(irs)
+            pl, pr = (int(getattr(b, "ptr", b)) for b in ir)
+        ac = (ArxAcoustics * (3 * max(k, 1)))() if acoustics else None
+        res = (ArxListenerResult * max(k, 1))()
+        ms = C.c_double(0.0)
+        check(lib().arx_render_listeners(self.handle, P.ctypes.data_as(C.POINTER(ArxListenerPose)), k, pl, pr, ac, res,
+                                         C.byref(ms)))
+        stats = np.frombuffer(res, dtype=LISTENER_RESULT_DTYPE, count=k).copy() if k else np.zeros(0, LISTENER_RESULT_DTYPE)
+        out_ac = None
+        if acoustics:
+            out_ac = [{name: _acoustics_dict(ac[3 * j + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)} for j in range(k)]
+        return {"ir": ir, "acoustics": out_ac, "stats": stats, "ms": float(ms.value)}
+
     def ray_order_buffer(self, count: int) -> dict:
         """arx_debug_ray_order_buffer: the first count slots (count x 4 floats) of the current frame
         set's direction buffer, the ray id of slot 0, the leading slots still in ray order and whether
@@ -466,15 +499,49 @@ def acoustics_from_histogram(left, right, sample_rate: int, unit: float = 1.0) -
 def write_acoustics_json(path: str, channels: dict) -> None:
     """{"left" | "right" | "sum": acoustics()} as JSON: invalid quantities (NaN) as null, an infinite
     clarity as the string "inf", valid as a sorted list."""
-    def plain(v):
-        if isinstance(v, (set, frozenset)):
-            return sorted(v)
-        if isinstance(v, float) and not np.isfinite(v):
-            return None if np.isnan(v) else ("inf" if v > 0 else "-inf")
-        return list(v) if isinstance(v, tuple) else v
-
     with open(path, "w") as fh:
-        json.dump({ch: {k: plain(v) for k, v in a.items()} for ch, a in channels.items()}, fh, indent=1)
+        json.dump({ch: {k: _json_plain(v) for k, v in a.items()} for ch, a in channels.items()}, fh, indent=1)
+        fh.write("\n")
+
+
+def _json_plain(v):
+    """write_acoustics_json's number formatting."""
+    if isinstance(v, (set, frozenset)):
+        return sorted(v)
+    if isinstance(v, float) and not np.isfinite(v):
+        return None if np.isnan(v) else ("inf" if v > 0 else "-inf")
+    return list(v) if isinstance(v, tuple) else v
+
+
+LISTENER_RESULT_DTYPE = np.dtype([("queries", "<u8"), ("receiver_hits", "<u8"), ("misses", "<u8"), ("candidate_rays", "<u8"),
+                                  ("route", "<i4"), ("reserved", "<i4"), ("reserved2", "<u8")])
+
+
+def listener_grid(lo, hi, nx: int, nz: int, y: float, yaw_deg: float = 0.0) -> np.ndarray:
+    """(nx * nz, 4) float32 poses (x, y, z, yaw_deg) for render_listeners: the centres of an nx x nz grid of
+    cells over [lo, hi] in x and z (lo / hi: (x, z) pairs or (x, y, z) triples whose y is ignored) at height
+    y, x fastest."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    x0, z0, x1, z1 = lo[0], lo[-1], hi[0], hi[-1]
+    xs = x0 + (np.arange(nx) + 0.5) * (x1 - x0) / nx
+    zs = z0 + (np.arange(nz) + 0.5) * (z1 - z0) / nz
+    out = np.empty((nx * nz, 4), np.float32)
+    out[:, 0] = np.tile(xs, nz)
+    out[:, 1] = y
+    out[:, 2] = np.repeat(zs, nx)
+    out[:, 3] = yaw_deg
+    return out
+
+
+def write_acoustic_map_json(path: str, poses, acoustics: list) -> None:
+    """A listener map as JSON: [{"pose": [x, y, z, yaw_deg], "left" | "right" | "sum": ...}] in pose order,
+    the channels written as write_acoustics_json writes them (NaN as null, an infinite clarity as "inf")."""
+    P = np.asarray(poses, np.float32).reshape(-1, 4)
+    if P.shape[0] != len(acoustics):
+        raise ValueError("one acoustics entry per pose")
+    with open(path, "w") as fh:
+        json.dump([{"pose": [float(v) for v in p], **{ch: {k: _json_plain(v) for k, v in a.items()} for ch, a in ac.items()}}
+                   for p, ac in zip(P, acoustics)], fh, indent=1)
         fh.write("\n")
 
 

@@ -638,6 +638,91 @@ arx_status arx_debug_path_filter_state(arx_renderer* r, int32_t* filtered, uint6
 /* Host only: bytes of the filter's planes for n_rays x max_bounces queries plus n_lists candidate lists. */
 uint64_t arx_debug_path_filter_bytes(uint64_t n_rays, uint32_t max_bounces, uint32_t n_lists);
 
+/* A batch of listeners rendered from one recorded path set in one call.
+ *
+ * Neither the path cache's records nor the path filter's planes depend on the listener, so a listener is
+ * only a question asked of stored data.  arx_render_listeners answers n of them:
+ *
+ *   saved = listener; for j in 0..n-1: arx_set_listener(poses[j]); arx_render(); [arx_analyze_ir()];
+ *   collect j;  arx_set_listener(saved)
+ *
+ * and its outputs are bit for bit that loop's: ir_left / ir_right the finalized f32 IRs (n x ir_len each,
+ * merged as arx_render merges them with is_mono; host or device memory, copied with hipMemcpyDefault on
+ * the renderer's stream like arx_memcpy; both NULL: no IR copies), acoustics arx_get_acoustics' structs
+ * (n x 3: channel 0, 1, 2 per listener; host memory; NULL: no analysis), results arx_get_stats' three
+ * counters per listener (host memory; NULL: none), *ms the device time of the whole call (a pair of
+ * events; recorded when ms is given or arx_set_timing is on).  Afterwards "the last frame" of every
+ * getter (arx_copy_ir, arx_get_stats, arx_histogram_device, arx_get_acoustics when acoustics was given,
+ * the IR generation streams follow) is pose n-1's, the listener is the one set before the call, and the
+ * path cache's records stay.  The per-launch timing ring (arx_trace_times) is advanced only by the poses
+ * that take the one-listener route.  n == 0: ARX_OK, nothing is touched.  The call synchronises once, at
+ * its end.
+ *
+ * ARX_ERR_INVALID_ARGUMENT: NULL r, NULL poses with n > 0, exactly one IR pointer NULL, a non-finite
+ * pose, more than one frame in flight, a caller's own stream (arx_set_stream), an attached histogram.
+ * ARX_ERR_NOT_READY without a scene.
+ *
+ * Routing.  While the cache holds no recording with filter state for the current key, the next pose runs
+ * through arx_set_listener + arx_render proper (the cache's usual warm-up: the key's first launch is
+ * traced, its second records and replays) and reports ARX_LISTENER_SINGLE.  Once it does, the remaining
+ * poses are answered in chunks by batched kernels: per chunk one clear, one receiver refit that places
+ * every listener's receiver into a slot of its own behind the renderer's receiver in the node and
+ * triangle arrays, one filter pass in which one read of the stored segments is tested against eight
+ * listeners' boxes, one candidate launch for the whole chunk, then the finalizes, analyses and copies.
+ * Where that state never comes (cache off, not cacheable or over its cap; filter off or without room;
+ * max_bounces > 64; a receiver too large for the device refit; no room for the scratch) every pose takes
+ * the one-listener route; a single pose takes it in place when the emitter lies inside its grown
+ * receiver box or its receiver cannot be put on the quantization grid.  So the call works wherever
+ * arx_render works; the batched kernels show only in `route` and on the clock.  Before the first chunk
+ * the quantization grid is grown, once, to hold the remaining poses' receivers, as a walking listener
+ * grows it; results do not depend on the grid.  A slot refit that leaves the grid ends the call with
+ * ARX_ERR_INTERNAL.
+ *
+ * Memory, OUTSIDE arx_debug_set_path_cache's max_bytes like the filter's planes: one scratch allocation
+ * per renderer, made by the first batched call, kept across calls, freed when it must grow and at
+ * arx_destroy.  Per listener of a chunk (arx_debug_listener_bytes):
+ *   96 x recv_nodes + 48 x recv_tris   its receiver slot (64-B and 32-B nodes, 48-B triangle records)
+ *   + 96 + 112                         its top node and its table entry
+ *   + 16 x ir_len + 128 + 336          histogram, counter block, three arx_acoustics
+ *   + 8 x ir_len                       its f32 IR pair
+ *   + 16 x rays + 16 x ceil(rays/1024) its candidate list and the list's heads
+ *   + 16 + 64 x ceil(rays/1024)        the candidate launch's work items
+ * (the slots live in the node and triangle arrays, which the first batched call widens), plus, whatever
+ * the chunk, one decay-curve buffer of 24 x ir_len B and the analysis kernels' scratch.  The automatic
+ * chunk is the largest count, at most 64, that keeps this within 512 MiB: at 1M rays, a 2-s IR at 48 kHz
+ * and the 1 020-triangle head, 18.5 MB per listener, so 28 listeners (495 MiB; 29 would be 512.5 MiB).
+ *
+ * Not offered here: groups (no arx_group_render_listeners), the C++ shim, app.py modes, frames in flight,
+ * and fades or convolution per listener. */
+typedef struct arx_listener_pose { float x, y, z, yaw_deg; } arx_listener_pose;          /* 16 B */
+#define ARX_LISTENER_BATCHED 0   /* answered by the batched kernels */
+#define ARX_LISTENER_SINGLE  1   /* went through the one-listener route (arx_set_listener + arx_render) */
+typedef struct arx_listener_result {                                                     /* 48 B, no implicit padding */
+    uint64_t queries, receiver_hits, misses;   /* arx_stats' three counters for this listener's frame */
+    uint64_t candidate_rays;                   /* batched route only, else 0 */
+    int32_t route;                             /* ARX_LISTENER_* */
+    int32_t reserved;                          /* 0 */
+    uint64_t reserved2;                        /* 0 */
+} arx_listener_result;
+arx_status arx_render_listeners(arx_renderer* r, const arx_listener_pose* poses, size_t n,
+                                float* ir_left, float* ir_right,      /* n*ir_len each, or both NULL */
+                                arx_acoustics* acoustics,             /* n*3 (channel 0, 1, 2 per listener), or NULL */
+                                arx_listener_result* results,         /* n, or NULL */
+                                double* ms);                          /* device time of the whole call, or NULL */
+/* listeners per chunk: 0 = automatic (the largest count whose scratch fits the budget), else forced, 1..64 */
+arx_status arx_debug_set_listener_chunk(arx_renderer* r, int32_t listeners);
+/* host only: scratch bytes of a chunk (slots, tops, per-listener table, histograms, counters, results, IRs,
+ * lists, heads): `listeners` times the per-listener sum above */
+uint64_t arx_debug_listener_bytes(uint64_t n_rays, int32_t ir_len, int64_t recv_nodes, int64_t recv_tris, int32_t listeners);
+/* host only: where chunk slot j lives -- node range, triangle range and top-node index -- for a scene of
+ * n_scene_nodes / n_scene_tris and a receiver of recv_nodes / recv_tris: out5 = {node begin, node end,
+ * triangle begin, triangle end, top}.  The tree is node 0, the scene's nodes, the renderer's own receiver;
+ * the chunk's tops follow at or above the kernels' LDS node cache, then the slots' nodes; the slots'
+ * triangles follow the renderer's own.  ARX_ERR_INVALID_ARGUMENT when any range would pass
+ * arx_debug_check_tree_limits' limits */
+arx_status arx_debug_listener_layout(int64_t n_scene_nodes, int64_t n_scene_tris, int64_t recv_nodes, int64_t recv_tris,
+                                     int32_t listeners, int32_t slot, int64_t out5[5]);
+
 /* Debug / parity hooks. */
 arx_status arx_debug_ray_directions(uint64_t seed, uint64_t first_ray, uint64_t count, float* h_out_xyz,
                                     int device);
