@@ -218,6 +218,13 @@ SIGNATURES = {
     "arx_stream_set_crossfade": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "arx_stream_get_crossfade": (C.c_int, [_P, _I32, _I32]),
     "arx_stream_crossfades": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "arx_convolute_walk": (C.c_int, [_P, _P, _P, C.c_size_t, _I32, C.c_size_t, _P, C.c_size_t, C.c_int32, C.c_int32,
+                                     C.c_int32, _P, _D]),
+    "arx_walk_blocks": (C.c_uint64, [C.c_uint64, C.c_int32, C.c_int32]),
+    "arx_walk_even_schedule": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, _I32]),
+    "arx_debug_walk_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32]),
+    "arx_debug_set_walk_tile": (C.c_int, [_P, C.c_int32]),
+    "arx_debug_walk_state": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "arx_group_create": (C.c_int, [C.POINTER(ArxConfig), _I32, C.c_int32, C.POINTER(_P)]),
     "arx_group_unique_id": (C.c_int, [C.c_char_p, C.c_size_t]),
     "arx_group_create_rank": (C.c_int, [C.POINTER(ArxConfig), C.c_int32, C.c_int32, C.c_char_p, C.c_size_t,

@@ -384,6 +384,7 @@ void arx_destroy(arx_renderer* r) {
     hipFree(r->d_tree_flag);
     free_path_cache(r->path_cache);
     free_listener_batch(r->listeners);
+    free_walk(r->walk);
     if (r->h_tree_flag) hipHostFree(r->h_tree_flag);
     hipFree(r->d_conv_in);
     hipFree(r->d_conv_out);

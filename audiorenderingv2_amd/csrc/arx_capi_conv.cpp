@@ -1,7 +1,8 @@
 // arx_capi_conv.cpp -- the convolution behind the C ABI (include/arx.h): the IR setters, the file
 // and live convolution plans and entry points (convoluteAudioFile and the live mode of
-// R/prebuild/obj_raytracer/AudioRenderer.cpp), and the streaming convolution (UPOLS,
-// arx_conv_stream.hip).
+// R/prebuild/obj_raytracer/AudioRenderer.cpp), the streaming convolution (UPOLS,
+// arx_conv_stream.hip) and the walk-through convolution over a per-block IR schedule
+// (arx_conv_walk.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -426,4 +427,187 @@ arx_status arx_stream_process(arx_stream* s, const double* h_in, size_t n_frames
     return ARX_OK;
 }
 
+// ---- walk-through convolution (arx_conv_walk.hip) ---------------------------------------------------
+
+arx_status arx_convolute_walk(arx_renderer* r, const float* ir_left, const float* ir_right, size_t n_irs,
+                              const int32_t* ir_of_block, size_t n_blocks, const double* in, size_t n_frames,
+                              int32_t block_frames, int32_t fade_frames, int32_t fade_shape, double* out, double* ms) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    if (n_blocks == 0) return ARX_OK;
+    if (!ir_left || !ir_right || !ir_of_block || !out || (n_frames > 0 && !in))
+        return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_irs == 0) return fail(ARX_ERR_INVALID_ARGUMENT, "no IRs");
+    const int32_t B = block_frames, F = fade_frames;
+    if (B <= 0 || B > 4096 || B > r->ir_len)
+        return fail(ARX_ERR_INVALID_ARGUMENT, "walk block of %d frames: must be in [1, min(4096, ir_len)]", B);
+    if (F < 0 || F > B) return fail(ARX_ERR_INVALID_ARGUMENT, "fade of %d frames: must be in [0, block = %d]", F, B);
+    if (fade_shape != ARX_FADE_LINEAR && fade_shape != ARX_FADE_HANN)
+        return fail(ARX_ERR_INVALID_ARGUMENT, "unknown fade shape %d", fade_shape);
+    if (n_blocks > (size_t)(INT32_MAX / 2)) return fail(ARX_ERR_INVALID_ARGUMENT, "%zu blocks are too many", n_blocks);
+    if (n_frames > n_blocks * (size_t)B)
+        return fail(ARX_ERR_INVALID_ARGUMENT, "%zu frames exceed %zu blocks of %d", n_frames, n_blocks, B);
+    for (size_t b = 0; b < n_blocks; ++b)
+        if (ir_of_block[b] < 0 || (size_t)ir_of_block[b] >= n_irs)
+            return fail(ARX_ERR_INVALID_ARGUMENT, "block %zu names IR %d of %zu", b, ir_of_block[b], n_irs);
+    WalkScratch& w = r->walk;
+    const size_t n = (size_t)r->ir_len;
+
+    // the schedule as items: the distinct IRs it names get slots in order of first use; a transition
+    // block's item of the previous IR goes in front of the block's own
+    std::vector<int32_t>& slot = w.h_slot;
+    slot.assign(n_irs, -1);
+    std::vector<int32_t> used;  // slot -> IR
+    size_t n_trans = 0;
+    for (size_t b = 0; b < n_blocks; ++b) {
+        const int32_t j = ir_of_block[b];
+        if (slot[(size_t)j] < 0) {
+            slot[(size_t)j] = (int32_t)used.size();
+            used.push_back(j);
+        }
+        if (F > 0 && b > 0 && j != ir_of_block[b - 1]) ++n_trans;
+    }
+    const size_t n_items = n_blocks + n_trans;
+    std::vector<int32_t>& tab = w.h_tables;
+    tab.assign(3 * n_items + n_trans, 0);
+    int32_t *item_block = tab.data(), *item_ir = item_block + n_items, *item_trans = item_ir + n_items,
+            *trans_block = item_trans + n_items;
+    size_t i = 0, t = 0;
+    for (size_t b = 0; b < n_blocks; ++b) {
+        const int32_t j = ir_of_block[b];
+        if (F > 0 && b > 0 && j != ir_of_block[b - 1]) {
+            item_block[i] = (int32_t)b;
+            item_ir[i] = slot[(size_t)ir_of_block[b - 1]];
+            item_trans[i++] = (int32_t)t;
+            trans_block[t++] = (int32_t)b;
+        }
+        item_block[i] = (int32_t)b;
+        item_ir[i] = slot[(size_t)j];
+        item_trans[i++] = -1;
+    }
+    const WalkLayout lay = walk_layout(r->ir_len, B, used.size(), n_blocks, n_trans, F);
+    if ((uint64_t)used.size() * (uint64_t)lay.P > (uint64_t)INT32_MAX)
+        return fail(ARX_ERR_INVALID_ARGUMENT, "%zu IRs of %d partitions are too many", used.size(), lay.P);
+
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    if (const arx_status wt = fif_wait_conv(r); wt != ARX_OK) return wt;
+    if (lay.total > w.bytes) {  // nothing of an earlier call is in flight: every call ends synchronised
+        hipFree(w.d_scratch);
+        w.d_scratch = nullptr;
+        w.bytes = 0;
+        w.tw_n = 0;
+        if (hipMalloc(&w.d_scratch, lay.total) != hipSuccess) {
+            (void)hipGetLastError();
+            w.d_scratch = nullptr;
+            return fail(ARX_ERR_OUT_OF_MEMORY, "the walk's scratch of %llu bytes", (unsigned long long)lay.total);
+        }
+        w.bytes = lay.total;
+    }
+    char* base = static_cast<char*>(w.d_scratch);
+    const bool timed = r->timing || ms != nullptr;
+    if (timed) {
+        if (!w.ev0) ARX_HIP(hipEventCreate(&w.ev0));
+        if (!w.ev1) ARX_HIP(hipEventCreate(&w.ev1));
+        ARX_HIP(hipEventRecord(w.ev0, r->stream));
+    }
+    if (w.tw_n != lay.N) {
+        if (w.h_tw.size() != 2 * (size_t)lay.N) walk_twiddle_table(lay.N, w.h_tw);
+        w.tw_n = 0;
+        ARX_HIP(hipMemcpyAsync(base + lay.tw, w.h_tw.data(), w.h_tw.size() * sizeof(double), hipMemcpyHostToDevice, r->stream));
+        w.tw_n = lay.N;
+    }
+    if (n_trans > 0) {
+        w.h_w.resize((size_t)F);
+        if (const arx_status fw = arx_stream_fade_weights(fade_shape, F, w.h_w.data()); fw != ARX_OK) return fw;
+        ARX_HIP(hipMemcpyAsync(base + lay.w, w.h_w.data(), (size_t)F * sizeof(double), hipMemcpyHostToDevice, r->stream));
+    }
+    ARX_HIP(hipMemcpyAsync(base + lay.tables, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
+    float* d_l = reinterpret_cast<float*>(base + lay.irs);
+    float* d_r = d_l + used.size() * n;
+    for (size_t u = 0; u < used.size();) {  // runs of consecutive IRs in one copy per ear
+        size_t e = u + 1;
+        while (e < used.size() && used[e] == used[e - 1] + 1) ++e;
+        const size_t src = (size_t)used[u] * n, bytes = (e - u) * n * sizeof(float);
+        ARX_HIP(hipMemcpyAsync(d_l + u * n, ir_left + src, bytes, hipMemcpyDefault, r->stream));
+        ARX_HIP(hipMemcpyAsync(d_r + u * n, ir_right + src, bytes, hipMemcpyDefault, r->stream));
+        u = e;
+    }
+    if (n_frames > 0) ARX_HIP(hipMemcpyAsync(base + lay.in, in, n_frames * sizeof(double), hipMemcpyDefault, r->stream));
+    WalkArgs a{};
+    a.scratch = w.d_scratch;
+    a.layout = lay;
+    a.ir_len = r->ir_len;
+    a.n_frames = (int64_t)n_frames;
+    a.n_blocks = (int32_t)n_blocks;
+    a.n_transitions = (int32_t)n_trans;
+    a.n_used = (int32_t)used.size();
+    a.fade = F;
+    a.tile = w.forced_tile > 0 ? w.forced_tile : kWalkTile;
+    ARX_HIP(launch_walk(a, r->stream));
+    ARX_HIP(hipMemcpyAsync(out, base + lay.out, 2 * n_blocks * (size_t)B * sizeof(double), hipMemcpyDefault, r->stream));
+    if (timed) ARX_HIP(hipEventRecord(w.ev1, r->stream));
+    if (const arx_status d = fif_done_conv(r); d != ARX_OK) return d;
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    if (ms) {
+        float el = 0.0f;
+        ARX_HIP(hipEventElapsedTime(&el, w.ev0, w.ev1));
+        *ms = (double)el;
+    }
+    w.state[0] = n_blocks;
+    w.state[1] = n_trans;
+    w.state[2] = used.size();
+    w.state[3] = (n_items + (size_t)a.tile - 1) / (size_t)a.tile;
+    w.state[4] = lay.total;
+    return ARX_OK;
+}
+
+uint64_t arx_walk_blocks(uint64_t n_frames, int32_t block_frames, int32_t ir_len) {
+    if (block_frames <= 0 || ir_len <= 0) return 0;
+    const uint64_t B = (uint64_t)block_frames;
+    return (n_frames + B - 1) / B + ((uint64_t)ir_len - 1 + B - 1) / B;
+}
+
+arx_status arx_walk_even_schedule(uint64_t n_input_blocks, uint64_t n_blocks, size_t n_irs, int32_t* ir_of_block) {
+    if (n_irs == 0 || n_irs > (size_t)INT32_MAX || (n_blocks > 0 && !ir_of_block))
+        return fail(ARX_ERR_INVALID_ARGUMENT, "bad schedule arguments");
+    int32_t last = 0;
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        if (b < n_input_blocks) {
+            const unsigned __int128 q = (unsigned __int128)b * n_irs / n_input_blocks;
+            last = (int32_t)std::min<unsigned __int128>(q, n_irs - 1);
+        }
+        ir_of_block[b] = last;
+    }
+    return ARX_OK;
+}
+
+uint64_t arx_debug_walk_bytes(int32_t ir_len, int32_t block_frames, uint64_t irs_used, uint64_t n_blocks,
+                              uint64_t n_transitions, int32_t fade_frames) {
+    if (ir_len <= 0 || block_frames <= 0 || block_frames > 4096 || block_frames > ir_len || fade_frames < 0 ||
+        fade_frames > block_frames)
+        return 0;
+    return walk_layout(ir_len, block_frames, irs_used, n_blocks, n_transitions, fade_frames).total;
+}
+
+arx_status arx_debug_set_walk_tile(arx_renderer* r, int32_t blocks) {
+    if (!r || blocks < 0 || blocks > kWalkTileMax)
+        return fail(ARX_ERR_INVALID_ARGUMENT, "walk tile: 0 (the product's) or 1..%d", kWalkTileMax);
+    r->walk.forced_tile = blocks;
+    return ARX_OK;
+}
+
+arx_status arx_debug_walk_state(arx_renderer* r, uint64_t out5[5]) {
+    if (!r || !out5) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::copy(r->walk.state, r->walk.state + 5, out5);
+    return ARX_OK;
+}
+
 }  // extern "C"
+
+void arx::free_walk(WalkScratch& w) {
+    hipFree(w.d_scratch);
+    if (w.ev0) hipEventDestroy(w.ev0);
+    if (w.ev1) hipEventDestroy(w.ev1);
+    const int32_t forced = w.forced_tile;
+    w = WalkScratch{};
+    w.forced_tile = forced;
+}

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "arx_conv_fft.hpp"
+#include "arx_conv_stream_common.hpp"
 #include "arx_kernels.hpp"
 
 namespace arx {
@@ -48,21 +49,6 @@ struct StreamPlan {
 };
 
 namespace {
-
-constexpr int kStreamThreads = 1024;  // lds_fft needs >= N/16 threads
-
-// The stream kernels' twiddles: W_N^e = hi[e >> 6] * lo[e & 63] from two small tables staged in LDS
-// after the N-point buffer (a global table lookup per butterfly put an L2 round trip into every
-// stage of these single-workgroup FFTs).
-__device__ __forceinline__ TwSplit stream_twiddles(double2* lds, int32_t N, int32_t lgN, const double2* __restrict__ tw) {
-    const int lgLo = lgN < 6 ? lgN : 6;
-    double2* hi = lds + N;
-    double2* lo = hi + (N >> lgLo);
-    for (int i = threadIdx.x; i < (N >> lgLo); i += kStreamThreads) hi[i] = tw[(size_t)i << lgLo];
-    for (int i = threadIdx.x; i < (1 << lgLo); i += kStreamThreads) lo[i] = tw[i];
-    return TwSplit{hi, lo, lgLo, N};
-}
-static size_t stream_lds(int32_t N) { return ((size_t)N + (size_t)(N >> 4) + 64) * sizeof(double2); }
 
 // G_p = FFT_N(hL[pB + i] + i hR[pB + i], i < B, zero padded): one workgroup per partition.
 __global__ __launch_bounds__(kStreamThreads) void stream_ir_kernel(const float* __restrict__ hl,
@@ -207,20 +193,15 @@ StreamPlan* stream_plan_create(int32_t ir_len, int32_t block, int device, char* 
     };
     if (ir_len <= 0 || block <= 0 || block > 4096) return bad("stream block must be in [1, 4096] frames");
     StreamPlan* p = new StreamPlan();
+    const StreamShape sh = stream_shape(ir_len, block);
     p->B = block;
-    p->lgN = ilog2(2 * (int64_t)block);
-    p->lgN = std::max(p->lgN, 4);
-    p->N = 1 << p->lgN;
-    p->P = (int32_t)(((int64_t)ir_len + block - 1) / block);
+    p->lgN = sh.lgN;
+    p->N = sh.N;
+    p->P = sh.P;
     p->n = ir_len;
-    p->scale = (double)ir_len / ((double)p->N * (double)(ir_len / 2));  // unnormalised IFFT, / (ir_len/2)
+    p->scale = sh.scale;
     hipSetDevice(device);
-    std::vector<double2> tw((size_t)p->N);
-    const long double two_pi = 6.283185307179586476925286766559L;
-    for (int64_t e = 0; e < p->N; ++e) {
-        const long double ang = two_pi * (long double)e / (long double)p->N;
-        tw[(size_t)e] = make_double2((double)cosl(ang), -(double)sinl(ang));
-    }
+    const std::vector<double2> tw = stream_twiddle_table(p->N);
     const size_t spec = (size_t)p->P * p->N * sizeof(double2);
     if (hipMalloc(&p->d_tw, (size_t)p->N * sizeof(double2)) != hipSuccess || hipMalloc(&p->d_G, spec) != hipSuccess ||
         hipMalloc(&p->d_X, spec) != hipSuccess || hipMalloc(&p->d_Z, 2 * (size_t)p->N * sizeof(double2)) != hipSuccess ||

@@ -1,8 +1,8 @@
 // arx_internal.hpp -- libarx.so internals shared by the C ABI translation units
 // (arx_capi.cpp: one renderer's lifecycle, frame sets, timing rings and getters; arx_scene.cpp: the
 // host-only scene image; arx_capi_trace.cpp: a frame -- device scene, trace, finalize, analysis;
-// arx_capi_conv.cpp: the file, live and streaming convolution; arx_group.cpp: ray-sharded multi-GPU
-// groups).
+// arx_capi_conv.cpp: the file, live, streaming and walk-through convolution; arx_group.cpp:
+// ray-sharded multi-GPU groups).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -172,6 +172,23 @@ struct ListenerBatch {
 };
 constexpr uint64_t kListenerBudget = 512ull << 20;  // scratch of an automatic chunk
 void free_listener_batch(ListenerBatch& b);
+// The walk-through convolution (arx_convolute_walk, include/arx.h): one scratch allocation per renderer
+// (walk_layout, arx_kernels.hpp), made by the first call, kept across calls and freed when it must grow and
+// at arx_destroy; outside the path cache's cap.
+struct WalkScratch {
+    int32_t forced_tile = 0;      // arx_debug_set_walk_tile: 0 the product's tile
+    void* d_scratch = nullptr;
+    uint64_t bytes = 0;
+    int32_t tw_n = 0;             // the scratch holds the twiddles of this FFT size (0: none)
+    std::vector<double> h_tw;     // their host copy (2 doubles each)
+    std::vector<int32_t> h_tables, h_slot;  // a call's item tables and IR slots, reused
+    std::vector<double> h_w;      // and its fade weights
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+    uint64_t state[5] = {};       // arx_debug_walk_state
+};
+constexpr int32_t kWalkTile = 8;      // items per MAC workgroup
+constexpr int32_t kWalkTileMax = 64;  // arx_debug_set_walk_tile
+void free_walk(WalkScratch& w);
 // What a replayed, filtered frame of the current key would launch, as trace_rays decides it (probe below).
 struct ReplayProbe {
     bool ready = false;  // the key is recorded with its filter state, and this launch would only replay
@@ -280,6 +297,7 @@ struct arx_renderer {
     uint64_t scene_gen = 0;        // scenes installed (set_scene_image): part of a frame set's OrderKey
     arx::PathCache path_cache;     // scene-only hits of the last repeated key (arx_debug_set_path_cache)
     arx::ListenerBatch listeners;  // arx_render_listeners' chunk scratch
+    arx::WalkScratch walk;         // arx_convolute_walk's scratch
     arx::QGrid qgrid{};
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "arx_layout.hpp"
 
@@ -200,5 +201,41 @@ int64_t stream_plan_blocks(const StreamPlan* p);  // processed since the last re
 int32_t stream_plan_fade(const StreamPlan* p);
 int32_t stream_plan_partitions(const StreamPlan* p);
 int32_t stream_plan_fft(const StreamPlan* p);
+
+// ---- walk-through convolution (arx_conv_walk.hip): a signal against a per-block IR schedule ----
+// The scratch of one call, as byte offsets (each part rounded up to 256 B; arx_debug_walk_bytes is
+// `total`), with the stream plan's sizes for ir_len frames in blocks of `block`.
+struct WalkLayout {
+    int32_t B, N, lgN, P;
+    double scale;
+    uint64_t tw;      // N twiddles (16 B each)
+    uint64_t w;       // fade weights (f64)
+    uint64_t G;       // irs_used x P x N partition spectra
+    uint64_t X;       // n_blocks x N input spectra
+    uint64_t Z;       // (n_blocks + n_transitions) x N accumulated spectra, one per item
+    uint64_t yprev;   // n_transitions x 2 fade: the previous IR's faded frames, zipped
+    uint64_t irs;     // irs_used x ir_len f32 left, then as many right
+    uint64_t in;      // n_blocks x block f64 input frames
+    uint64_t out;     // n_blocks x 2 block f64 output frames, zipped
+    uint64_t tables;  // per item its block, IR slot and transition (-1: none), then per transition its block (int32)
+    uint64_t total;
+};
+WalkLayout walk_layout(int32_t ir_len, int32_t block, uint64_t irs_used, uint64_t n_blocks, uint64_t n_transitions,
+                       int32_t fade);
+// W_N^e as 2 N doubles: what the scratch's `tw` must hold.
+void walk_twiddle_table(int32_t N, std::vector<double>& out);
+// X rows the MAC's LDS ring holds for a tile of this many items (the launch's LDS: rows x 4 KiB).
+int32_t walk_tile_rows(int32_t tile);
+struct WalkArgs {
+    void* scratch;       // laid out by `layout`; tw, w, irs, in and tables filled, out written
+    WalkLayout layout;
+    int32_t ir_len;
+    int64_t n_frames;    // input frames in `in`, <= n_blocks * B
+    int32_t n_blocks, n_transitions, n_used;
+    int32_t fade;        // frames blended on a transition block (unused without one)
+    int32_t tile;        // items per MAC workgroup, >= 1
+};
+// The five launches (IR spectra, forward, MAC, inverse, blend) on s; nothing waits on the host.
+hipError_t launch_walk(const WalkArgs& a, hipStream_t s);
 
 }  // namespace arx

@@ -283,6 +283,82 @@ class AudioRenderer:
             out_ac = [{name: _acoustics_dict(ac[3 * j + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)} for j in range(k)]
         return {"ir": ir, "acoustics": out_ac, "stats": stats, "ms": float(ms.value)}
 
+    def set_walk_tile(self, items: int) -> None:
+        """arx_debug_set_walk_tile: items per multiply-accumulate workgroup of convolute_walk (0: the
+        product's tile, else 1..64); the same bits either way."""
+        check(lib().arx_debug_set_walk_tile(self.handle, int(items)))
+
+    def walk_state(self) -> dict:
+        """arx_debug_walk_state: the last convolute_walk's blocks, transition blocks, distinct IRs
+        transformed, tiles launched and scratch bytes."""
+        out = (C.c_uint64 * 5)()
+        check(lib().arx_debug_walk_state(self.handle, out))
+        return dict(zip(("blocks", "transitions", "irs_transformed", "tiles", "scratch_bytes"), (int(v) for v in out)))
+
+    def convolute_walk(self, irs, ir_of_block, samples, block_frames: int = 4096, crossfade_frames: int = 0,
+                       fade: str | int = "hann", n_irs: int | None = None, n_frames: int | None = None, out=None) -> dict:
+        """arx_convolute_walk: `samples` convolved with the IR ir_of_block[b] on output block b, crossfaded
+        over the first crossfade_frames frames of every block whose IR differs from the block before -- bit
+        for bit the loop of set_ir_device + LiveStream.process_device over the blocks, in one call that
+        leaves the renderer's IR and streams alone.  irs: a pair of [K, ir_len] float32 arrays, or a pair of
+        DeviceBuffers / device pointers of K * ir_len floats each with n_irs=K (render_listeners' irs).
+        samples: an array (converted to f64), or a DeviceBuffer / device pointer of f64 frames with
+        n_frames.  out: None (a host array is returned) or a DeviceBuffer / device pointer of
+        2 * len(ir_of_block) * block_frames doubles (returned as given).  Returns {"out": the frames as
+        [len(ir_of_block) * block_frames, 2] L/R, "ms": the call's device time}."""
+        sched = np.ascontiguousarray(ir_of_block, np.int32).reshape(-1)
+        nb, B = sched.size, int(block_frames)
+        keep = []  # host arrays the call reads
+        if n_irs is None:
+            L, R = (np.ascontiguousarray(a, np.float32) for a in irs)
+            if L.shape != R.shape or L.ndim != 2 or L.shape[1] != self.ir_length:
+                raise ValueError("irs: a pair of [K, ir_len] arrays")
+            keep += [L, R]
+            k, pl, pr = L.shape[0], L.ctypes.data, R.ctypes.data
+        else:
+            k = int(n_irs)
+            pl, pr = (int(getattr(b, "ptr", b)) for b in irs)
+        if n_frames is None:
+            x = np.ascontiguousarray(samples, np.float64).reshape(-1)
+            keep.append(x)
+            nf, px = x.size, x.ctypes.data
+        else:
+            nf, px = int(n_frames), int(getattr(samples, "ptr", samples))
+        host_out = None
+        if out is None:
+            host_out = np.empty((nb * max(B, 0), 2), np.float64)
+            po_ = host_out.ctypes.data
+        else:
+            po_ = int(getattr(out, "ptr", out))
+        ms = C.c_double(0.0)
+        check(lib().arx_convolute_walk(self.handle, pl or None, pr or None, k, sched.ctypes.data_as(C.POINTER(C.c_int32)), nb,
+                                       px or None, nf, B, int(crossfade_frames), _fade_shape(fade), po_ or None,
+                                       C.byref(ms)))
+        del keep
+        return {"out": host_out if out is None else out, "ms": float(ms.value)}
+
+    def auralise_walk(self, poses, samples, block_frames: int = 4096, crossfade_frames: int | None = None,
+                      fade: str | int = "hann") -> dict:
+        """A walk made audible on the device: render_listeners over the poses into device buffers, the
+        poses spread evenly over the input's blocks (walk_schedule over walk_blocks, the last pose ringing
+        out the tail), then convolute_walk on those buffers -- the IRs never visit the host.
+        crossfade_frames=None: a whole block.  Returns {"out": [n_blocks * block_frames, 2] L/R frames,
+        "ir_of_block", "render_ms", "ms": the convolution's device time}."""
+        P = np.asarray(poses, np.float32).reshape(-1, 4)
+        x = np.ascontiguousarray(samples, np.float64).reshape(-1)
+        B = int(block_frames)
+        F = B if crossfade_frames is None else int(crossfade_frames)
+        sched = walk_schedule(x.size, B, self.ir_length, P.shape[0])
+        dev = self.settings.device
+        bufs = [DeviceBuffer(dev, max(P.shape[0] * self.ir_length * 4, 4)) for _ in range(2)]
+        try:
+            rl = self.render_listeners(P, irs=tuple(bufs), acoustics=False)
+            res = self.convolute_walk(tuple(bufs), sched, x, B, F, fade, n_irs=P.shape[0])
+        finally:
+            for b in bufs:
+                b.close()
+        return {"out": res["out"], "ir_of_block": sched, "render_ms": rl["ms"], "ms": res["ms"]}
+
     def ray_order_buffer(self, count: int) -> dict:
         """arx_debug_ray_order_buffer: the first count slots (count x 4 floats) of the current frame
         set's direction buffer, the ray id of slot 0, the leading slots still in ray order and whether
@@ -570,6 +646,22 @@ def fade_weights(shape: str | int, n: int) -> np.ndarray:
     w = np.empty(max(int(n), 0), np.float64)
     check(lib().arx_stream_fade_weights(_fade_shape(shape), int(n), w.ctypes.data_as(C.POINTER(C.c_double))))
     return w
+
+
+def walk_blocks(n_frames: int, block_frames: int, ir_len: int) -> int:
+    """arx_walk_blocks (host only): ceil(n_frames / block) + ceil((ir_len - 1) / block), the blocks of a
+    convolute_walk until the tail has rung out; 0 for invalid arguments."""
+    return int(lib().arx_walk_blocks(int(n_frames), int(block_frames), int(ir_len)))
+
+
+def walk_schedule(n_frames: int, block_frames: int, ir_len: int, n_irs: int) -> np.ndarray:
+    """arx_walk_even_schedule over walk_blocks (host only): the int32 ir_of_block of a walk that spreads
+    n_irs IRs evenly over the input's ceil(n_frames / block) blocks and rings out the tail with the last."""
+    nb = walk_blocks(n_frames, block_frames, ir_len)
+    n_in = -(-int(n_frames) // int(block_frames)) if block_frames > 0 else 0
+    out = np.zeros(nb, np.int32)
+    check(lib().arx_walk_even_schedule(n_in, nb, int(n_irs), out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
 
 
 class LiveStream:

@@ -692,8 +692,10 @@ uint64_t arx_debug_path_filter_bytes(uint64_t n_rays, uint32_t max_bounces, uint
  * chunk is the largest count, at most 64, that keeps this within 512 MiB: at 1M rays, a 2-s IR at 48 kHz
  * and the 1 020-triangle head, 18.5 MB per listener, so 28 listeners (495 MiB; 29 would be 512.5 MiB).
  *
- * Not offered here: groups (no arx_group_render_listeners), the C++ shim, app.py modes, frames in flight,
- * and fades or convolution per listener. */
+ * Not offered here: groups (no arx_group_render_listeners), the C++ shim, app.py modes and frames in
+ * flight.  Turning the IR set into audio -- a signal convolved with a per-block schedule over these IRs,
+ * crossfaded at every change -- is arx_convolute_walk (below), which takes ir_left / ir_right as this
+ * call wrote them. */
 typedef struct arx_listener_pose { float x, y, z, yaw_deg; } arx_listener_pose;          /* 16 B */
 #define ARX_LISTENER_BATCHED 0   /* answered by the batched kernels */
 #define ARX_LISTENER_SINGLE  1   /* went through the one-listener route (arx_set_listener + arx_render) */
@@ -722,6 +724,85 @@ uint64_t arx_debug_listener_bytes(uint64_t n_rays, int32_t ir_len, int64_t recv_
  * arx_debug_check_tree_limits' limits */
 arx_status arx_debug_listener_layout(int64_t n_scene_nodes, int64_t n_scene_tris, int64_t recv_nodes, int64_t recv_tris,
                                      int32_t listeners, int32_t slot, int64_t out5[5]);
+
+/* Walk-through convolution: one signal against a per-block IR schedule, in one call.
+ *
+ * ir_left / ir_right hold n_irs IRs of ir_len frames each (arx_render_listeners' layout; ir_len and the
+ * sample rate are the renderer's), ir_of_block[b] in [0, n_irs) names the IR of output block b (host
+ * memory), in holds n_frames <= n_blocks * block_frames f64 frames, out receives 2 * n_blocks *
+ * block_frames doubles, zipped L/R.  ir_left, ir_right, in and out may each be host or device memory on
+ * the renderer's device: they are copied with hipMemcpyDefault on the renderer's stream, as
+ * arx_render_listeners copies its IRs.  The call needs no scene.  With B = block_frames, F = fade_frames,
+ * the output is bit for bit that of this loop, run on a fresh stream of the same renderer:
+ *
+ *   s = arx_stream_create(r, B); arx_stream_set_crossfade(s, F, fade_shape)
+ *   for b in 0 .. n_blocks-1:
+ *       j = ir_of_block[b]
+ *       if b == 0 or j != ir_of_block[b-1]: arx_set_ir_device(r, ir_left + j*ir_len, ir_right + j*ir_len, ir_len)
+ *       m = clamp(n_frames - b*B, 0, B)
+ *       arx_stream_process_device(s, m ? in + b*B : NULL, m, out + 2*b*B)
+ *
+ * So block b > 0 is a transition block exactly when F > 0 and ir_of_block[b] != ir_of_block[b-1]: it
+ * fades from the previous block's IR to its own over its first F frames with arx_stream_fade_weights'
+ * values; with F == 0 an IR change is the hard switch; blocks past the input ring out the tail
+ * (arx_walk_blocks counts them).  Unlike the loop the call leaves the renderer alone: its IR, its IR
+ * generation, its arx_stream objects, its listener and its path cache do not change, and a live stream of
+ * the same renderer produces the same bits with or without a walk call in between.  The call orders
+ * itself on the renderer's stream as arx_stream_process_device does, synchronises once, at its end, and
+ * reports in *ms its device time, copies included (a pair of events; recorded when ms is given or
+ * arx_set_timing is on).
+ *
+ * How: nothing runs block after block.  The distinct IRs the schedule names are transformed once each
+ * (one named several times, A B A included, once; one never named not at all), every block's input
+ * spectrum is made in one launch, one multiply-accumulate launch covers every (block, IR) item -- a
+ * transition block is two items -- in tiles of consecutive items that share the input spectra they read,
+ * one launch inverts every item and one blends every transition block.  Per item the arithmetic is the
+ * stream's kernels' (DESIGN.md section 6.6).
+ *
+ * n_blocks == 0: ARX_OK, nothing is touched.  ARX_ERR_INVALID_ARGUMENT: NULL r, ir_left, ir_right,
+ * ir_of_block or out; NULL in with n_frames > 0; n_irs == 0; an index outside [0, n_irs); n_frames >
+ * n_blocks * B; B outside [1, min(4096, ir_len)]; F outside [0, B]; an unknown fade_shape.
+ * ARX_ERR_OUT_OF_MEMORY when the scratch cannot be allocated; the renderer stays usable.
+ *
+ * Memory, OUTSIDE arx_debug_set_path_cache's max_bytes: one scratch allocation per renderer, made by the
+ * first call, kept across calls, freed when it must grow and at arx_destroy.  With N = the power of two
+ * >= 2 B (at least 16), P = ceil(ir_len / B), U = the distinct IRs named, T = the transition blocks,
+ * a call needs (arx_debug_walk_bytes), every term rounded up to a multiple of 256:
+ *   16 N                    the twiddles
+ *   + 8 F                   the fade weights
+ *   + 16 N x P x U          the IRs' partition spectra
+ *   + 16 N x n_blocks       the input spectra
+ *   + 16 N x (n_blocks + T) the accumulated spectrum of every item
+ *   + 16 F x T              the previous IR's faded frames
+ *   + 8 ir_len x U          the named IRs, f32 left and right
+ *   + 8 B x n_blocks        the input frames
+ *   + 16 B x n_blocks       the output frames
+ *   + 16 (n_blocks + T)     the item tables
+ * (48 kHz x 2 s, B = 4096, 728 blocks over 64 IRs with a whole-block fade: 525 MB.)
+ *
+ * Not offered: groups, the C++ shim, app.py modes, fades longer than a block, float32 output. */
+arx_status arx_convolute_walk(arx_renderer* r,
+                              const float* ir_left, const float* ir_right, size_t n_irs, /* n_irs x ir_len each */
+                              const int32_t* ir_of_block, size_t n_blocks,               /* host; values in [0, n_irs) */
+                              const double* in, size_t n_frames,                         /* n_frames <= n_blocks * block_frames */
+                              int32_t block_frames, int32_t fade_frames, int32_t fade_shape,
+                              double* out,                                               /* 2 * n_blocks * block_frames, zipped L/R */
+                              double* ms);                                               /* device time of the call, or NULL */
+/* Host only: ceil(n_frames / B) + ceil((ir_len - 1) / B), the blocks until the tail of n_frames input
+ * frames has rung out; 0 for a non-positive block_frames or ir_len. */
+uint64_t arx_walk_blocks(uint64_t n_frames, int32_t block_frames, int32_t ir_len);
+/* Host only: n_irs IRs spread evenly over the input.  Block b < n_input_blocks gets
+ * min(n_irs - 1, b * n_irs / n_input_blocks) (integer division); later blocks -- the tail -- keep the last
+ * input block's value (0 without input blocks).  ARX_ERR_INVALID_ARGUMENT: n_irs == 0 or above INT32_MAX,
+ * NULL ir_of_block with n_blocks > 0. */
+arx_status arx_walk_even_schedule(uint64_t n_input_blocks, uint64_t n_blocks, size_t n_irs, int32_t* ir_of_block);
+/* Host only: scratch bytes of a call by the formula above; 0 for arguments the call would reject. */
+uint64_t arx_debug_walk_bytes(int32_t ir_len, int32_t block_frames, uint64_t irs_used, uint64_t n_blocks,
+                              uint64_t n_transitions, int32_t fade_frames);
+/* items per multiply-accumulate workgroup: 0 = the product's tile (8), else forced, 1..64 */
+arx_status arx_debug_set_walk_tile(arx_renderer* r, int32_t blocks);
+/* the last call's blocks, transition blocks, distinct IRs transformed, tiles launched and scratch bytes */
+arx_status arx_debug_walk_state(arx_renderer* r, uint64_t out5[5]);
 
 /* Debug / parity hooks. */
 arx_status arx_debug_ray_directions(uint64_t seed, uint64_t first_ray, uint64_t count, float* h_out_xyz,
