@@ -25,11 +25,14 @@ OBJDIR = os.path.join(PKG, "_obj")
 LIB = os.path.join(PKG, "libarx.so")
 ARCH = os.environ.get("ARX_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["arx_trace.hip", "arx_receiver.hip", "arx_conv.hip", "arx_conv_stream.hip", "arx_conv_walk.hip", "arx_acoustics.hip", "arx_capi.cpp",
+SOURCES = ["arx_trace.hip", "arx_replay.hip", "arx_receiver.hip", "arx_conv.hip", "arx_conv_stream.hip", "arx_conv_walk.hip", "arx_acoustics.hip", "arx_capi.cpp",
            "arx_scene.cpp", "arx_capi_trace.cpp", "arx_capi_conv.cpp", "arx_group.cpp", "arx_bvh.cpp", "arx_io.cpp", "arx_wide.cpp"]
 # the file / live convolution's kernels and the FFT device code under them: the files conv_source_id hashes
 CONV_KERNEL_FILES = ("arx_conv_fft.hpp", "arx_conv_kernels.hpp")
-HEADERS = ["arx_layout.hpp", "arx_kernels.hpp", "arx_bvh.hpp", "arx_internal.hpp", "arx_wide.hpp", "arx_scene_share.hpp",
+# the trace program (trace_kernel, its pre-pass and launchers), the query's device code and the layouts: the
+# files trace_source_id hashes.  arx_replay.hip, which runs from the trace kernel's records, is not among them
+TRACE_KERNEL_FILES = ("arx_trace.hip", "arx_trace_device.hpp", "arx_layout.hpp")
+HEADERS = ["arx_layout.hpp", "arx_trace_device.hpp", "arx_kernels.hpp", "arx_bvh.hpp", "arx_internal.hpp", "arx_wide.hpp", "arx_scene_share.hpp",
            "arx_conv_stream_common.hpp", *CONV_KERNEL_FILES]
 
 COMMON = [
@@ -39,11 +42,12 @@ COMMON = [
 ]
 
 
-# Per-file flags.  arx_trace.hip: no SLP vectorisation -- packed f32 VALU (v_pk_add/mul/fma_f32,
+# Per-file flags.  arx_trace.hip and arx_replay.hip (the files that compile arx_trace_device.hpp's triangle
+# test and shade()): no SLP vectorisation -- packed f32 VALU (v_pk_add/mul/fma_f32,
 # which the SLP vectoriser forms from the triangle test's and shading's scalar arithmetic) costs more
 # issue cycles than the scalar pairs it replaces (MI355X_MICROARCH.md); C3 trace -2 %, C2 -4 %
 # (profiles/r03/ab_leaf2_noslp.txt).  Same arithmetic, bit-identical results.
-FILE_FLAGS = {"arx_trace.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"arx_trace.hip": ["-fno-slp-vectorize"], "arx_replay.hip": ["-fno-slp-vectorize"]}
 
 
 def hipcc() -> str:
@@ -73,12 +77,13 @@ def _source_id(files: tuple[str, ...], defines: tuple[str, ...]) -> str:
 
 
 def trace_source_id(defines: tuple[str, ...] = ()) -> str:
-    """64-bit identity of the trace kernel a build compiles: a hash of its source files and of the
-    experiment macros (not the measurement-only ones).  Compiled into the library
+    """64-bit identity of the trace kernel a build compiles: a hash of its source files
+    (TRACE_KERNEL_FILES) and of the experiment macros (not the measurement-only ones).  Compiled into the library
     (arx_trace_kernel_id) and stored in every PMC profile's guard, so bench.py uses a stored
     profile only for the kernel it was taken of."""
-    # arx_kernels.hpp (host launcher declarations) is not part of it: its edits do not change the kernel
-    return _source_id(("arx_trace.hip", "arx_layout.hpp"), defines)
+    # arx_kernels.hpp (host launcher declarations) and arx_replay.hip (the replay kernels) are not part
+    # of it: their edits do not change the kernel
+    return _source_id(TRACE_KERNEL_FILES, defines)
 
 
 def conv_source_id(defines: tuple[str, ...] = ()) -> str:

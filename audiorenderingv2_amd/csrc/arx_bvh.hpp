@@ -112,7 +112,7 @@ QGrid make_qgrid(const float lo[3], const float hi[3], double margin_frac = 0.1)
 // True if the box [lo, hi] lies inside the grid with room for the outward rounding.
 bool qgrid_contains(const QGrid& g, const float lo[3], const float hi[3]);
 // Quantized copy of coded nodes: every child box is rounded outward to the grid with a margin of
-// 0.1 step (for the kernel's f32 slab arithmetic, see arx_trace.hip node_step7);
+// 0.1 step (for the kernel's f32 slab arithmetic, see arx_trace_device.hpp node_step);
 // empty children become a one-step box at the grid corner.  False if a box leaves the grid.
 bool quantize_nodes16(const BvhNode* coded, size_t n, const QGrid& g, QNode2* out);
 }  // namespace arx

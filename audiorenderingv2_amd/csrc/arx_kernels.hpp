@@ -11,6 +11,7 @@ struct arx_acoustics;  // include/arx.h
 
 namespace arx {
 
+// ---- the trace program (arx_trace.hip; the query's device code: arx_trace_device.hpp) ----
 // Trace kernel (raygen + traversal + closest-hit + histogram, fused) over rays
 // [a.ray_begin, a.ray_end); cus = compute units of the device (persistent grid size).
 // Quantized nodes when a.qnodes is set, else the f32 coded nodes; the global-memory stack when
@@ -30,28 +31,13 @@ uint32_t trace_pool_share();
 hipError_t launch_order_pool(const void* dirs_in, void* dirs_out, const unsigned short* cost, uint32_t* bins, uint64_t n,
                              hipStream_t s);
 size_t order_bins_bytes();
-// The path cache (arx_renderer::PathCache).  trace_can_cache: the launch takes a 16-bit LDS-stack
+// The path cache's recording (arx_renderer::PathCache).  trace_can_cache: the launch takes a 16-bit LDS-stack
 // instance, pool or small -- the ones with a recording instance.  launch_path_record: that instance's
 // recording twin over the scene alone, on a.dirs as it stands (no directions are made), storing every
 // query's closest hit into a.rec; a.counters (a.clear_counters of them zeroed first)
-// and a.cursor must be a scratch block, a.hist is not touched.  launch_path_replay: the frame from
-// those records and the receiver sub-tree (replay_kernel), with the clear a.clear_bins /
-// a.clear_counters ask for in front; a.dirs must be the buffer the records were made on.
+// and a.cursor must be a scratch block, a.hist is not touched.
 bool trace_can_cache(const TraceArgs& a, bool force_global_stack);
 hipError_t launch_path_record(const TraceArgs& a, int cus, hipStream_t s);
-hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s);
-// The filtered replay of a recording that stored its queries' start state (a.gstack of
-// launch_path_record pointed at the filter's planes, arx_layout.hpp): the clear, filter_kernel over
-// every slot, replay_cand_kernel over the candidates it listed.  max_bounces in [1, kFilterMaxBounces];
-// f.list and f.heads belong to the frame set whose stream s is.  Results are launch_path_replay's.
-hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, hipStream_t s);
-// The filtered replay for a chunk of `listeners` table entries at once (filter_multi_kernel: one read of the
-// segment plane serves kListenerFilterWidth listeners; replay_cand_multi_kernel: one launch for the whole
-// chunk).  a is the replay's arguments (dirs and rec the cache's); its hist, counters and center and f's
-// list and heads are taken from each entry instead, the box from the entry's top node in a.cnodes.  Per
-// listener the results are launch_path_replay_filtered's.  No clear: the caller clears the chunk's block.
-hipError_t launch_listeners_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
-                                   int32_t listeners, hipStream_t s);
 // Nodes below this index are answered by the trace kernels' LDS copy (0: this build has none).
 int32_t trace_node_cache();
 // Lanes of the largest persistent trace grid (columns of the global traversal stack).
@@ -73,6 +59,23 @@ hipError_t trace_kernel_occupancy(int fmt, int instance, int* vgprs, int* waves_
 bool trace_uses_small_block(const TraceArgs& a, int cus, bool force_global_stack);
 // identity of the trace kernel in this build (build.py trace_source_id; arx_trace_kernel_id)
 uint64_t trace_kernel_source_id();
+
+// ---- the replay family (arx_replay.hip): frames from launch_path_record's records ----
+// launch_path_replay: the frame from those records and the receiver sub-tree (replay_kernel), with the
+// clear a.clear_bins / a.clear_counters ask for in front; a.dirs must be the buffer the records were made on.
+hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s);
+// The filtered replay of a recording that stored its queries' start state (a.gstack of
+// launch_path_record pointed at the filter's planes, arx_layout.hpp): the clear, filter_kernel over
+// every slot, replay_cand_kernel over the candidates it listed.  max_bounces in [1, kFilterMaxBounces];
+// f.list and f.heads belong to the frame set whose stream s is.  Results are launch_path_replay's.
+hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, hipStream_t s);
+// The filtered replay for a chunk of `listeners` table entries at once (filter_multi_kernel: one read of the
+// segment plane serves kListenerFilterWidth listeners; replay_cand_multi_kernel: one launch for the whole
+// chunk).  a is the replay's arguments (dirs and rec the cache's); its hist, counters and center and f's
+// list and heads are taken from each entry instead, the box from the entry's top node in a.cnodes.  Per
+// listener the results are launch_path_replay_filtered's.  No clear: the caller clears the chunk's block.
+hipError_t launch_listeners_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
+                                   int32_t listeners, hipStream_t s);
 
 // ---- room-acoustic parameters (arx_acoustics.hip): decay curves and ISO 3382-1 statistics ----
 constexpr int kScanWorkgroup = 1, kScanTiled = 2;  // arx_debug_set_scan_shape

@@ -167,7 +167,7 @@ struct TraceArgs {
 constexpr uint64_t kPathRecordBytes = 24;
 static_assert(sizeof(TraceArgs) == 240, "TraceArgs: the product kernels' hidden arguments start at this offset");
 
-// The path filter (filter_kernel / replay_cand_kernel, arx_trace.hip): what every recorded query
+// The path filter (filter_kernel / replay_cand_kernel, arx_replay.hip): what every recorded query
 // started from, so that a replayed frame runs only the queries whose segment crosses the receiver's box.
 // One allocation of three planes, laid out [bounce][slot] like the records, n = rays of the launch:
 //   segment  (max_bounces + 1) * n x 16 B  {pos.x, pos.y, pos.z, dist}: row b is the state before query
@@ -208,7 +208,7 @@ struct FilterArgs {
 constexpr float kFilterMargin = 0.0078125f;    // 2^-7 m
 constexpr float kFilterEndSlack = 0.00390625f;  // 2^-8 m: the recording's bound on |stored end - ray's own hit point|, per axis
 
-// A batch of listeners (arx_render_listeners; filter_multi_kernel / replay_cand_multi_kernel, arx_trace.hip,
+// A batch of listeners (arx_render_listeners; filter_multi_kernel / replay_cand_multi_kernel, arx_replay.hip,
 // and the receiver refit's chunk launch, arx_receiver.hip).  A chunk of J listeners is answered from one
 // recording at once: each listener j has a slot -- a placed copy of the receiver sub-tree and a top node of
 // its own -- in the node and triangle arrays behind the renderer's own receiver range, and an entry of

@@ -1,0 +1,644 @@
+// arx_replay.hip -- the replay family: frames answered from the records of trace_kernel<RECORD>
+// (arx_trace.hip) and the receiver sub-tree alone.  replay_kernel replays every query of every ray
+// (the path cache); filter_kernel + replay_cand_kernel replay only the queries whose segment meets
+// the receiver's box (the path filter); filter_multi_kernel + cand_work_kernel +
+// replay_cand_multi_kernel do that for a chunk of listeners in one call.
+//
+// Every query here is the same arithmetic on the same bits as the traced frame's (the functions of
+// arx_trace_device.hpp), and each step the kernels share -- the kernel set-up, the record read, the
+// receiver query, a candidate's chain, the filter's prelude and its output -- exists once, below.
+// Not part of the trace kernel's identity (build.py TRACE_KERNEL_FILES): an edit here leaves the
+// stored trace profiles valid.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "arx_kernels.hpp"
+#include "arx_layout.hpp"
+#include "arx_trace_device.hpp"
+
+#ifndef ARX_REPLAY_BLOCK
+#define ARX_REPLAY_BLOCK 256  // replay_kernel's block; design experiments only (build.py --exp)
+#endif
+
+namespace arx {
+namespace {
+
+// What a replay kernel sets up once: the LDS stack (with its sentinel row), node_step's top-of-tree
+// copy, the node and triangle descriptors, and the planes of the recording -- the records, and with
+// FilterArgs the filter's segment / state / meta planes (arx_layout.hpp).
+template <int BLOCK>
+struct ReceiverCtx {
+    using Stack = LdsStack<BLOCK, kLdsStack>;
+    Stack stk;
+    const uint4* ncache;
+    __amdgpu_buffer_rsrc_t nrs, trs;
+    arx_i32x4 qrs;
+    const float4* tbase;
+    uint64_t n;  // rays of the recording
+    const float4* __restrict__ rec_hit;
+    const float2* __restrict__ rec_bary;
+    const float4* __restrict__ seg;
+    const float4* __restrict__ state;
+    const unsigned short* __restrict__ meta;
+};
+
+// Called once by every lane of the block, before any divergence (it holds a barrier when the build
+// has a node cache), and once per kernel: the stack and the node copy are this function's own
+// __shared__ arrays, one per BLOCK, so a second call in a kernel would hand out the same stack.
+template <int BLOCK>
+__device__ __forceinline__ ReceiverCtx<BLOCK> receiver_ctx(const TraceArgs& a) {
+    __shared__ int stk_lds[(kLdsStack + 1) * BLOCK];
+    __shared__ uint4 ncache[kNodeCache > 0 ? 2 * kNodeCache : 1];  // node_step's top-of-tree copy, as in trace_kernel
+    if constexpr (kNodeCache > 0) {
+        const uint4* q = reinterpret_cast<const uint4*>(a.qnodes);
+        for (int i = threadIdx.x; i < 2 * kNodeCache; i += BLOCK) ncache[i] = q[i];
+        __syncthreads();
+    }
+    ReceiverCtx<BLOCK> c;
+    c.stk.base = stk_lds + threadIdx.x;
+    stk_lds[threadIdx.x] = -1;  // the dummy row under the stack (LdsStack::kSentinel)
+    c.ncache = ncache;
+    c.nrs = buffer_rsrc(a.qnodes, ARX_TRACE_IDXEN ? (short)sizeof(QNode2) : (short)0);
+    c.qrs = qnodes_rsrc4(a.qnodes);
+    c.tbase = reinterpret_cast<const float4*>(a.tris);
+    c.trs = buffer_rsrc(c.tbase);
+    c.n = a.ray_end - a.ray_begin;
+    c.rec_hit = reinterpret_cast<const float4*>(a.rec);
+    c.rec_bary = reinterpret_cast<const float2*>(c.rec_hit + (uint64_t)a.max_bounces * c.n);
+    c.seg = nullptr;
+    c.state = nullptr;
+    c.meta = nullptr;
+    return c;
+}
+template <int BLOCK>
+__device__ __forceinline__ ReceiverCtx<BLOCK> receiver_ctx(const TraceArgs& a, const FilterArgs& f) {
+    ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a);
+    c.seg = reinterpret_cast<const float4*>(f.planes);
+    c.state = c.seg + path_filter_seg_rows(a.max_bounces) * c.n;
+    c.meta = reinterpret_cast<const unsigned short*>(c.state + (uint64_t)a.max_bounces * c.n);
+    return c;
+}
+
+// The cached scene-only closest hit of record `at` (bounce * n + slot), as trace_kernel<RECORD> stored it.
+template <int BLOCK>
+__device__ __forceinline__ void load_record(const ReceiverCtx<BLOCK>& c, uint64_t at, Best& best) {
+    const float4 h = c.rec_hit[at];
+    const float2 b = c.rec_bary[at];
+    best.t = h.x;
+    best.id = __float_as_int(h.y);
+    best.unit = __float_as_int(h.z);
+    best.v = h.w;
+    best.w = b.x;
+    best.det = b.y;
+}
+
+// One closest-hit query over a receiver sub-tree alone, starting from the hit already in `best`: for
+// the active lanes setup_ray, the grid form of the slab planes (trace_kernel's, on the same bits) and
+// one step on node `top` with its child 0 forced off (node 0: the scene; a listener's own top node:
+// empty) -- on to the receiver's root or done, so a segment that misses the receiver's box costs that
+// one step.  Then, for the whole wave, the sub-tree: node steps while any lane has one, then the
+// pending leaves.  The loop's ballots are wave-wide: every lane of the wave must call this from
+// uniform control flow, each with its own `active`.
+template <int BLOCK>
+__device__ __forceinline__ void receiver_query(const ReceiverCtx<BLOCK>& c, const TraceArgs& a, bool active,
+                                               const RayState& s, int top, Ray& r, Best& best) {
+    using Stack = typename ReceiverCtx<BLOCK>::Stack;
+    // The traversal's state stays local and the caller keeps only the hit, so that the closest-hit
+    // registers are not copied at the callers' loop joins (profiles/r14/replay_split.json).
+    Trav t;
+    t.best = best;
+    float oix = 0.f, oiy = 0.f, oiz = 0.f;
+    t.node = -1;
+    t.sp = 0;
+    if (active) {
+        setup_ray(r, s.pos, s.dir);
+        oix = (r.o[0] - a.qgrid.origin[0]) * r.inv[0];
+        oiy = (r.o[1] - a.qgrid.origin[1]) * r.inv[1];
+        oiz = (r.o[2] - a.qgrid.origin[2]) * r.inv[2];
+        r.inv[0] *= a.qgrid.scale[0];
+        r.inv[1] *= a.qgrid.scale[1];
+        r.inv[2] *= a.qgrid.scale[2];
+#if ARX_TRACE_SIGNSEL && ARX_TRACE_BITFLOAT
+        oix = __builtin_fmaf(8388608.0f, r.inv[0], oix);
+        oiy = __builtin_fmaf(8388608.0f, r.inv[1], oiy);
+        oiz = __builtin_fmaf(8388608.0f, r.inv[2], oiz);
+#endif
+        t.node = top;
+        node_step<kFmtQ16, Stack, false, true>(r, oix, oiy, oiz, t, c.stk, c.nrs, c.ncache, c.qrs);
+    }
+    while (true) {
+        const unsigned long long m_node = __ballot(t.node >= 0);
+        const unsigned long long m_leaf = __ballot(t.node <= -2);
+        if ((m_node | m_leaf) == 0ull) break;
+        if (m_node != 0ull) {
+            if (t.node >= 0) node_step<kFmtQ16, Stack, false>(r, oix, oiy, oiz, t, c.stk, c.nrs, c.ncache, c.qrs);
+        } else {
+            leaf_step<kFmtQ16>(c.trs, r, t, c.stk);
+        }
+    }
+    best = t.best;
+}
+
+// The path cache's replay (arx_capi_trace.cpp, PathCache): a frame of a key whose scene-only closest
+// hits trace_kernel<RECORD> stored.  A ray's path through the static scene does not depend on the
+// listener; the receiver enters a query only as one more candidate for the closest hit, take_hit's
+// lexicographic minimum of (t, id) does not depend on the order candidates are tested in, and a
+// receiver hit ends the ray.  So each query here is the cached hit, a closest-hit query over the
+// receiver sub-tree alone that starts from it, and the same shade(): the histogram and the counters
+// come out bit for bit as the full traversal's.  The receiver sub-tree is entered by one step on the
+// top node with child 0 (the scene) forced off: a segment that misses the receiver's box costs that
+// one step.  One ray per lane, slot = lane's global index into the cache's own direction copy
+// (a.dirs); a plain grid, every lane's work about the same, so no pool and no persistent waves.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void replay_kernel(TraceArgs a) {
+    const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a);
+    const int lane = threadIdx.x;
+    const uint64_t slot = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t n_q = 0, n_rx = 0, n_miss = 0;
+    RayState s;
+    s.depth = -1;
+    bool active = false;
+    if (slot < c.n) {
+        ray_init(a, s, a.ray_begin + slot);
+        active = wants_query(a, s);
+    }
+    Ray r;
+    Best best;
+    while (__ballot(active) != 0ull) {
+        if (active) {
+            // (fetching the next bounce's record a query ahead measured even: the load is not what a
+            // query waits for, profiles/r10/ab_path_cache.txt)
+            load_record(c, (uint64_t)s.depth * c.n + slot, best);
+            ++n_q;
+        }
+        receiver_query(c, a, active, s, 0, r, best);
+        if (active) {
+            shade(a, c.tbase, s, r, best, n_rx, n_miss);
+            active = wants_query(a, s);
+        }
+    }
+    flush_counters(a, n_q, n_rx, n_miss, lane);
+}
+
+// ------------------------------------------------------- the path filter ---
+// A filtered replay: the recording also stored what every query started from (arx_layout.hpp), so the
+// queries of a ray no longer depend on each other, and a frame needs only those whose segment can
+// touch the receiver.  filter_kernel finds them, replay_cand_kernel runs them.
+//
+// filter_kernel, a lane per slot on a plain grid: the ray's rows of the segment plane, each read once
+// (the previous row stays in registers), segment [pos_b, pos_b+1] against the receiver's box, one bit
+// per bounce.  Always candidates: a last query that missed (its segment has no end) or that ended on a
+// receiver-marked triangle of the scene (its shading needs a.center), and every query of a ray the
+// recording flagged (kFilterWild).  No atomic anywhere: a block compacts its candidate rays into its own
+// stretch of the frame set's list and leaves a 16-B head -- how many, their candidate queries, and the
+// summed query counts of its rays without a candidate, which replay_cand_kernel adds to the frame's counters.
+//
+// The box is the f32 box of the top node's receiver child (cnodes[0], written by the receiver refit on
+// the same stream, so it follows the listener with no host copy), grown by a.grow on every side.  Why
+// that is enough -- the one place where exactness is argued and not inherited:
+//   - The traced frame ends a ray on the receiver in query b only if take_hit accepted a receiver
+//     triangle at some t <= best.t, best.t being the scene-only hit the record holds: the point
+//     X = pos_b + t * dir_b of the segment [pos_b, Q], Q = pos_b + best.t * dir_b.
+//   - X lies in that triangle up to the triangle test's rounding: t is the barycentric mean of the
+//     vertices' depths along the ray's major axis, so X is off the triangle by a few ulps of the
+//     coordinates' magnitude M times at most sqrt(3) (the major axis holds >= 1/sqrt(3) of |dir|),
+//     far below 1e-5 * M; and the triangle lies inside the box, which the refit pads by 1e-5 * M.
+//   - The stored segment ends at E = P + 1e-3 * dir', not at Q.  The recording checked, for this very
+//     query, |Q - E| <= kFilterEndSlack = 2^-8 m on every axis (else the ray is kFilterWild) -- no bound on
+//     |dir| or on how well t and the barycentric P agree is assumed.  X = pos_b + u (Q - pos_b), u in
+//     [0, 1], so the stored segment's point pos_b + u (E - pos_b) is within 2^-8 m of X per axis.
+//   - So a box grown by 2^-8 m plus the rounding above is met by the stored segment whenever the
+//     receiver can be hit.  kFilterMargin is 2^-7 m: twice that; the box is about 2 m wide, the slack costs nothing.
+//   - The slab test's own rounding: u = (plane - p) * rcp(d) carries a relative error below 2^-21
+//     (two subtractions, a 1-ulp reciprocal, a product), which is the exact u of a plane moved by
+//     |plane - p| * 2^-21 <= 2^-20 * M.  The host adds 2^-18 * M to a.grow, M from the grid that holds
+//     the scene, the emitter and the receiver.  A NaN anywhere compares as "candidate".
+__device__ __forceinline__ bool segment_meets_box(float4 p, float4 q, const float (&lo)[3], const float (&hi)[3]) {
+    const float pp[3] = {p.x, p.y, p.z}, qq[3] = {q.x, q.y, q.z};
+    float un = 0.0f, uf = 1.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float d = qq[k] - pp[k];
+        if (fabsf(d) < 1e-20f) d = (d < 0.0f) ? -1e-20f : 1e-20f;
+        const float inv = __builtin_amdgcn_rcpf(d);
+        const float u0 = (lo[k] - pp[k]) * inv, u1 = (hi[k] - pp[k]) * inv;
+        un = fmaxf(un, fminf(u0, u1));
+        uf = fminf(uf, fmaxf(u0, u1));
+    }
+    return !(un > uf);
+}
+
+// A filter lane's ray: its meta word (0 for an idle lane), the queries it ran, and the wave's longest
+// count, which bounds the segment loop so that every lane's loads stay unconditional.
+struct FilterRay {
+    uint32_t m, count, cmax;
+};
+__device__ __forceinline__ FilterRay filter_ray_prelude(const TraceArgs& a, bool have, uint64_t slot,
+                                                        const unsigned short* __restrict__ meta) {
+    FilterRay fr;
+    fr.m = have ? meta[slot] : 0u;
+    fr.count = min(fr.m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
+    uint32_t cmax = fr.count;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, off, 64));
+    fr.cmax = __builtin_amdgcn_readfirstlane(cmax);
+    return fr;
+}
+// The queries that are candidates whatever the box says: a flagged last query, every query of a wild ray.
+__device__ __forceinline__ unsigned long long filter_fix_mask(uint32_t m, uint32_t count, unsigned long long mask) {
+    if (count > 0u) {
+        const unsigned long long last = 1ull << (count - 1u), all = last | (last - 1ull);
+        if (m & (kFilterMiss | kFilterMarked)) mask |= last;
+        if (m & kFilterWild) mask = all;
+    }
+    return mask;
+}
+
+// The filter's output for one listener, with no atomic anywhere.  (One atomic per wave on a list cursor
+// and the counters, 15 625 waves at C3 on two cache lines, was what bound this kernel: 0.26 ms for a 41 us
+// read, profiles/r11/ab_path_filter.txt.)  The block compacts its candidates into its own stretch of the
+// list, [blockIdx * BLOCK, ...): at most one entry per slot, so the stretch is the block's slots.  Its
+// head holds how many, their queries, and the queries of the rays that need no replay, which the
+// candidate kernel adds to the frame's counters with its own.  Two halves with the caller's
+// __syncthreads() between them: filter_sums leaves each wave's partial sums in the listener's three
+// [BLOCK / 64] LDS rows and returns the wave's candidate ballot; filter_store writes the entries and the head.
+__device__ __forceinline__ unsigned long long filter_sums(unsigned long long mask, uint32_t count, uint32_t* w_cand,
+                                                          uint32_t* w_cq, uint32_t* w_nq) {
+    const bool cand = mask != 0ull;
+    const unsigned long long ballot = __ballot(cand);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned int cq = cand ? (unsigned int)__popcll(mask) : 0u, nq = cand ? 0u : count;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cq += __shfl_xor(cq, off, 64);
+        nq += __shfl_xor(nq, off, 64);
+    }
+    if (lane == 0) {
+        w_cand[wave] = (uint32_t)__popcll(ballot);
+        w_cq[wave] = cq;
+        w_nq[wave] = nq;
+    }
+    return ballot;
+}
+template <int BLOCK>
+__device__ __forceinline__ void filter_store(unsigned long long mask, unsigned long long ballot, uint64_t slot,
+                                             FilterCand* list, void* heads, const uint32_t* w_cand,
+                                             const uint32_t* w_cq, const uint32_t* w_nq) {
+    constexpr int WAVES = BLOCK / 64;
+    const int wave = threadIdx.x >> 6;
+    uint32_t before = 0u, t_cand = 0u, t_cq = 0u, t_nq = 0u;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        before += w < wave ? w_cand[w] : 0u;
+        t_cand += w_cand[w];
+        t_cq += w_cq[w];
+        t_nq += w_nq[w];
+    }
+    if (mask != 0ull) {
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+        FilterCand c;
+        c.mask = mask;
+        c.slot = (uint32_t)slot;
+        c.pad = 0u;
+        // before + rank < the block's candidates <= its slots below n, so inside the list's n entries
+        list[(uint64_t)blockIdx.x * BLOCK + before + rank] = c;
+    }
+    // (a missed last query is always a candidate: no misses among the rays counted here)
+    if (threadIdx.x == 0) reinterpret_cast<uint4*>(heads)[blockIdx.x] = make_uint4(t_cand, t_cq, t_nq, 0u);
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void filter_kernel(TraceArgs a, FilterArgs f) {
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool have = gid < n;
+    const uint64_t slot = have ? gid : n - 1;  // n >= 1 (launch_path_replay_filtered); idle lanes read in bounds
+    const float4* __restrict__ seg = reinterpret_cast<const float4*>(f.planes);
+    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(
+        seg + (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+    // the receiver's box: the same address for every lane, so scalar loads, once per wave
+    const BvhNode& top = a.cnodes[0];
+    const float lo[3] = {top.b[0] - f.grow, top.b[2] - f.grow, top.c[2] - f.grow};
+    const float hi[3] = {top.b[1] + f.grow, top.b[3] + f.grow, top.c[3] + f.grow};
+    const FilterRay fr = filter_ray_prelude(a, have, slot, meta);
+    unsigned long long mask = 0ull;
+    float4 p = seg[slot];
+#pragma unroll 4
+    for (uint32_t b = 0; b < fr.cmax; ++b) {
+        // rows past the ray's last are not its own: it re-reads its last row (count <= max_bounces exists)
+        const float4 q = seg[(uint64_t)min(b + 1u, fr.count) * n + slot];
+        const bool hit = segment_meets_box(p, q, lo, hi);
+        mask |= (hit && b < fr.count) ? (1ull << b) : 0ull;
+        p = q;
+    }
+    mask = filter_fix_mask(fr.m, fr.count, mask);
+    __shared__ uint32_t w_cand[BLOCK / 64], w_cq[BLOCK / 64], w_nq[BLOCK / 64];
+    const unsigned long long ballot = filter_sums(mask, fr.count, w_cand, w_cq, w_nq);
+    __syncthreads();
+    filter_store<BLOCK>(mask, ballot, slot, f.list, f.heads, w_cand, w_cq, w_nq);
+}
+
+// One entry of a candidate list, entry i of `list` for the lanes that `have` one: the chain of its
+// queries.  For each set bit, ascending: the stored state and the cached hit, then replay_kernel's
+// query (receiver_query, entered at node `top`) on the same bits with the same functions.  If the receiver
+// gave the closest hit, or this is the ray's flagged last query, shade() runs and the ray ends; else
+// nothing is shaded, the next query's state being stored already.  A ray that does not end here ran its
+// recorded count of queries.  Wave-wide like receiver_query: every lane of the wave calls it, from
+// uniform control flow.
+template <int BLOCK>
+__device__ __forceinline__ void cand_chain(const ReceiverCtx<BLOCK>& c, const TraceArgs& a,
+                                           const FilterCand* __restrict__ list, uint64_t i, bool have, int top,
+                                           uint32_t& n_q, uint32_t& n_rx, uint32_t& n_miss) {
+    const uint64_t n = c.n;
+    unsigned long long mask = 0ull;
+    uint64_t slot = 0;
+    uint32_t m = 0u;
+    if (have) {
+        const FilterCand e = list[i];
+        mask = e.mask;
+        slot = e.slot < n ? e.slot : n - 1;
+        m = c.meta[slot];
+    }
+    const uint32_t count = min(m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
+    mask &= count > 0u ? ((1ull << (count - 1u)) << 1) - 1ull : 0ull;  // bits of queries the ray ran
+    bool active = mask != 0ull, ended = false;
+    Ray r;
+    Best best;
+    while (__ballot(active) != 0ull) {
+        RayState s;
+        s.depth = -1;
+        int unit0 = -1;
+        if (active) {
+            const uint32_t b = (uint32_t)__builtin_ctzll(mask);
+            mask &= mask - 1ull;
+            const uint64_t at = (uint64_t)b * n + slot;
+            const float4 sp = c.seg[at], sd = c.state[at];
+            load_record(c, at, best);
+            s.pos = make_float3(sp.x, sp.y, sp.z);
+            s.dist = sp.w;
+            s.dir = make_float3(sd.x, sd.y, sd.z);
+            s.e = sd.w;
+            s.depth = (int)b;
+            unit0 = best.unit;
+        }
+        receiver_query(c, a, active, s, top, r, best);
+        if (active) {
+            const bool flagged = (uint32_t)s.depth + 1u == count && (m & (kFilterMiss | kFilterMarked)) != 0u;
+            if (best.unit != unit0 || flagged) {
+                n_q += (uint32_t)s.depth + 1u;
+                shade(a, c.tbase, s, r, best, n_rx, n_miss);
+                ended = true;
+                active = false;
+            } else if (mask == 0ull) {
+                active = false;
+            }
+        }
+    }
+    if (have && !ended) n_q += count;
+}
+
+// replay_cand_kernel: a 64-lane block per 64 entries of each filter block's stretch of the list; the
+// stretch's head says how many it holds (device memory: nothing waits on the host), a lane per
+// candidate ray, each running its entry's chain (cand_chain).  The queries of the rays filter_kernel
+// retired come in through the heads.
+__global__ __launch_bounds__(64) void replay_cand_kernel(TraceArgs a, FilterArgs f) {
+    constexpr int BLOCK = 64;
+    // Block (fb, c) takes candidates [64 c, 64 c + 64) of filter block fb's stretch, so a stretch full of
+    // candidates is sixteen waves' work, not one wave's sixteen rounds: the pool's slots are ordered
+    // longest first with the rays the receiver ended in front (launch_order_pool), so the candidates
+    // crowd into a few stretches, and a wave per stretch took 0.93 ms at C3 where this takes 0.20.  Most
+    // blocks read their head and leave, before anything else is set up; a stretch's first block stays
+    // to add the head's query count.
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint32_t chunks = kFilterBlock / BLOCK;
+    const uint64_t fblocks = (n + kFilterBlock - 1) / kFilterBlock;
+    const uint64_t fb = blockIdx.x / chunks;
+    const uint32_t base = (blockIdx.x % chunks) * BLOCK;
+    if (fb >= fblocks) return;
+    const uint4 head = reinterpret_cast<const uint4*>(f.heads)[fb];  // the same address for every lane
+    const uint32_t n_cand = min(head.x, kFilterBlock);
+    if (base > 0u && base >= n_cand) return;
+    const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a, f);
+    const int lane = threadIdx.x;
+    uint32_t n_q = 0, n_rx = 0, n_miss = 0;
+    if (base == 0u && lane == 0) n_q += head.z;
+    const uint64_t i = fb * kFilterBlock + base + lane;
+    cand_chain(c, a, f.list, i, base + lane < n_cand && i < n, 0, n_q, n_rx, n_miss);
+    flush_counters(a, n_q, n_rx, n_miss, lane);
+}
+
+// ------------------------------------------------- a batch of listeners ---
+// arx_render_listeners: many listeners answered from one recording.  Neither the records nor the filter's
+// planes depend on the listener, so a listener is a box to cull the stored segments against and a receiver
+// sub-tree to query; a chunk of them has its sub-trees placed side by side (ListenerEntry, arx_layout.hpp).
+//
+// filter_multi_kernel is filter_kernel with the segment in registers tested against F listeners' boxes:
+// one read of the segment plane serves F listeners (blockIdx.y picks the F).  Per listener the arithmetic,
+// the mask, the block's stretch of that listener's list and its head are filter_kernel's for that listener
+// alone: the box is the same six floats of the listener's top node with the same grow, and the prelude,
+// segment_meets_box, the mask's fix-up and the two halves of the output are the same functions, the
+// compaction running per listener on its own ballot.  The boxes wait in LDS, six floats a listener, read
+// by every lane at the same address.
+template <int BLOCK, int F>
+__global__ __launch_bounds__(BLOCK) void filter_multi_kernel(TraceArgs a, FilterArgs f,
+                                                             const ListenerEntry* __restrict__ tbl, int32_t listeners) {
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool have = gid < n;
+    const uint64_t slot = have ? gid : n - 1;  // n >= 1 (launch_listeners_replay); idle lanes read in bounds
+    const float4* __restrict__ seg = reinterpret_cast<const float4*>(f.planes);
+    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(
+        seg + (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+    const int j0 = (int)blockIdx.y * F;  // this pass's listeners: [j0, min(j0 + F, listeners))
+    __shared__ float box[F][6];
+    if (threadIdx.x < F) {
+        const int i = threadIdx.x;
+        float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f};
+        if (j0 + i < listeners) {
+            const BvhNode& top = a.cnodes[tbl[j0 + i].top];  // child 1: the slot's receiver, as the refit left it
+            lo[0] = top.b[0] - f.grow; lo[1] = top.b[2] - f.grow; lo[2] = top.c[2] - f.grow;
+            hi[0] = top.b[1] + f.grow; hi[1] = top.b[3] + f.grow; hi[2] = top.c[3] + f.grow;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            box[i][k] = lo[k];
+            box[i][3 + k] = hi[k];
+        }
+    }
+    __syncthreads();
+    const FilterRay fr = filter_ray_prelude(a, have, slot, meta);
+    unsigned long long mask[F];
+#pragma unroll
+    for (int i = 0; i < F; ++i) mask[i] = 0ull;
+    float4 p = seg[slot];
+#pragma unroll 2
+    for (uint32_t b = 0; b < fr.cmax; ++b) {
+        const float4 q = seg[(uint64_t)min(b + 1u, fr.count) * n + slot];
+        const unsigned long long bit = b < fr.count ? (1ull << b) : 0ull;
+#pragma unroll
+        for (int i = 0; i < F; ++i) {
+            const float lo[3] = {box[i][0], box[i][1], box[i][2]}, hi[3] = {box[i][3], box[i][4], box[i][5]};
+            mask[i] |= segment_meets_box(p, q, lo, hi) ? bit : 0ull;
+        }
+        p = q;
+    }
+    // all F partial sums, one barrier, then all F outputs
+    __shared__ uint32_t w_cand[F][BLOCK / 64], w_cq[F][BLOCK / 64], w_nq[F][BLOCK / 64];
+    unsigned long long ballot[F];
+#pragma unroll
+    for (int i = 0; i < F; ++i) {
+        mask[i] = filter_fix_mask(fr.m, fr.count, mask[i]);
+        ballot[i] = filter_sums(mask[i], fr.count, w_cand[i], w_cq[i], w_nq[i]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < F; ++i) {
+        if (j0 + i >= listeners) break;  // a ragged last pass (the same for the whole block)
+        const ListenerEntry& e = tbl[j0 + i];
+        filter_store<BLOCK>(mask[i], ballot[i], slot, e.list, e.heads, w_cand[i], w_cq[i], w_nq[i]);
+    }
+}
+
+// cand_work_kernel, a block per listener: the listener's work items in stretch order -- for every stretch
+// its first 64 entries (that item also adds the stretch's head) and every further 64 that hold a
+// candidate -- as (stretch * 16 + part) words behind their count (ListenerEntry::work).  replay_cand_kernel
+// launches a block for each of a frame's 16 x stretches parts and lets the empty ones leave; with a chunk
+// of listeners those are hundreds of thousands of blocks that only read a head, and dispatching them was
+// what the chunk's candidate launch took (profiles/r12/listeners_kernel_stats.csv).  No atomic: a block-wide
+// scan of the parts per stretch, tile after tile.
+__global__ __launch_bounds__(1024) void cand_work_kernel(const ListenerEntry* __restrict__ tbl, uint32_t fblocks) {
+    constexpr int BLOCK = 1024, WAVES = BLOCK / 64;
+    const ListenerEntry& e = tbl[blockIdx.x];
+    const uint4* __restrict__ heads = reinterpret_cast<const uint4*>(e.heads);
+    __shared__ uint32_t w_sum[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t done = 0u;  // items of the tiles before this one (the same in every thread)
+    for (uint32_t t0 = 0u; t0 < fblocks; t0 += BLOCK) {
+        const uint32_t fb = t0 + threadIdx.x;
+        uint32_t parts = 0u;
+        if (fb < fblocks) parts = max(1u, (min(heads[fb].x, kFilterBlock) + 63u) / 64u);
+        uint32_t incl = parts;  // inclusive scan within the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t v = (uint32_t)__shfl_up((int)incl, off, 64);
+            if (lane >= off) incl += v;
+        }
+        if (lane == 63) w_sum[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0u, total = 0u;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            before += w < wave ? w_sum[w] : 0u;
+            total += w_sum[w];
+        }
+        const uint32_t at = done + before + incl - parts;  // <= 16 * fb: inside the 16 * fblocks words
+        for (uint32_t c = 0u; c < parts; ++c) e.work[4u + at + c] = fb * 16u + c;
+        done += total;
+        __syncthreads();  // w_sum is written again by the next tile
+    }
+    if (threadIdx.x == 0) e.work[0] = done;
+}
+
+// replay_cand_multi_kernel is replay_cand_kernel with the listener taken from blockIdx.y: the histogram,
+// the counters, shade()'s centre, the list and the heads come from the listener's table entry (the same for
+// the whole block, so they stay scalar), and the query enters the listener's own top node instead of node 0
+// -- child 0 empty and skipped, child 1 the slot's receiver root -- so it is the same arithmetic on the same
+// boxes and triangles.  The per-ray chain is the same function, cand_chain.
+// What differs is which block takes which 64 entries: a listener's blocks walk its work items
+// (cand_work_kernel) gridDim.x apart, so neighbouring items -- the candidates crowd into few stretches --
+// go to different blocks, and no block is launched only to leave.  A stretch's first item also adds the
+// stretch's candidate rays to the listener's tally (e.cand).
+__global__ __launch_bounds__(64) void replay_cand_multi_kernel(TraceArgs a, FilterArgs f,
+                                                               const ListenerEntry* __restrict__ tbl) {
+    constexpr int BLOCK = 64;
+    const ListenerEntry& e = tbl[blockIdx.y];
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint64_t fblocks = (n + kFilterBlock - 1) / kFilterBlock;
+    const uint32_t n_items = min(e.work[0], (uint32_t)min(fblocks * (kFilterBlock / BLOCK), (uint64_t)0xffffffffu));
+    if (blockIdx.x >= n_items) return;
+    for (int k = 0; k < 3; ++k) a.center[k] = e.center[k];
+    a.hist = e.hist;
+    a.counters = e.counters;
+    const FilterCand* list = e.list;
+    const int top = e.top;
+    const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a, f);
+    const int lane = threadIdx.x;
+    uint32_t n_q = 0, n_rx = 0, n_miss = 0;
+    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const uint32_t word = e.work[4u + item];  // the same address for every lane, like the head
+        const uint64_t fb = min((uint64_t)(word >> 4), fblocks - 1);
+        const uint32_t base = (word & 15u) * BLOCK;
+        const uint4 head = reinterpret_cast<const uint4*>(e.heads)[fb];
+        const uint32_t n_cand = min(head.x, kFilterBlock);
+        if (base == 0u && lane == 0) {
+            n_q += head.z;
+            if (head.x) atomicAdd(e.cand, (unsigned long long)head.x);
+        }
+        const uint64_t i = fb * kFilterBlock + base + lane;
+        cand_chain(c, a, list, i, base + lane < n_cand && i < n, top, n_q, n_rx, n_miss);
+    }
+    flush_counters(a, n_q, n_rx, n_miss, lane);
+}
+
+}  // namespace
+
+hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.hist || !a.counters || !a.rec)
+        return hipErrorInvalidValue;
+    if (a.clear_bins > 0 || a.clear_counters > 0) {
+        const hipError_t e = launch_clear(a.hist, a.clear_bins, a.counters, a.clear_counters, s);
+        if (e != hipSuccess) return e;
+    }
+    constexpr int RB = ARX_REPLAY_BLOCK;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    hipLaunchKernelGGL(replay_kernel<RB>, dim3((unsigned)((n_rays + RB - 1) / RB)), dim3(RB), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.hist || !a.counters || !a.rec || !a.cnodes || !f.planes ||
+        !f.list || !f.heads || a.max_bounces < 1 || a.max_bounces > kFilterMaxBounces)
+        return hipErrorInvalidValue;
+    if (a.clear_bins > 0 || a.clear_counters > 0) {
+        const hipError_t e = launch_clear(a.hist, a.clear_bins, a.counters, a.clear_counters, s);
+        if (e != hipSuccess) return e;
+    }
+    constexpr int FB = (int)kFilterBlock;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    const uint64_t fblocks = (n_rays + FB - 1) / FB;
+    // a wave per 64 entries of every filter block's stretch of the list
+    const uint64_t g2 = fblocks * (FB / 64);
+    if (g2 > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_kernel<FB>, dim3((unsigned)fblocks), dim3(FB), 0, s, a, f);
+    hipLaunchKernelGGL(replay_cand_kernel, dim3((unsigned)g2), dim3(64), 0, s, a, f);
+    return hipGetLastError();
+}
+
+hipError_t launch_listeners_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
+                                   int32_t listeners, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.rec || !a.cnodes || !f.planes || !d_table ||
+        listeners < 1 || listeners > kListenerChunkMax || a.max_bounces < 1 || a.max_bounces > kFilterMaxBounces ||
+        a.ray_end <= a.ray_begin)
+        return hipErrorInvalidValue;
+    constexpr int FB = (int)kFilterBlock;
+    constexpr int F = (int)kListenerFilterWidth;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    const uint64_t fblocks = (n_rays + FB - 1) / FB;
+    const uint64_t g2 = fblocks * (FB / 64);
+    if (g2 > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((filter_multi_kernel<FB, F>), dim3((unsigned)fblocks, (unsigned)((listeners + F - 1) / F)), dim3(FB), 0,
+                       s, a, f, d_table, listeners);
+    // the candidates: each listener's work items, then a fixed number of blocks that walk them
+    hipLaunchKernelGGL(cand_work_kernel, dim3((unsigned)listeners), dim3(1024), 0, s, d_table, (uint32_t)fblocks);
+    constexpr uint64_t kCandBlocks = 8192;  // of one wave each: what the device holds at once, and a half more
+    const uint64_t per = std::min<uint64_t>(g2, (kCandBlocks + (uint64_t)listeners - 1) / (uint64_t)listeners);
+    hipLaunchKernelGGL(replay_cand_multi_kernel, dim3((unsigned)per, (unsigned)listeners), dim3(64), 0, s, a, f, d_table);
+    return hipGetLastError();
+}
+
+}  // namespace arx

@@ -92,7 +92,7 @@ arx_status arx::check_scene_input(const float* tri_v, const float* tri_abs, int6
 }
 
 // The trace kernel addresses nodes and triangle records through buffer resources with 32-bit byte
-// offsets and num_records 0x7fffffff (arx_trace.hip buffer_rsrc; a load past it returns zeros, which
+// offsets and num_records 0x7fffffff (arx_trace_device.hpp buffer_rsrc; a load past it returns zeros, which
 // the leaf step uses for idle lanes): every record must end below 2^31 bytes, or a triangle would read
 // back as zeros (det 0, a silently dropped hit).  44.7 M triangle records / 33.5 M coded nodes.
 arx_status arx::check_buffer_offsets(size_t n_nodes, size_t n_tris) {

@@ -35,11 +35,13 @@ def test_library_exports_every_declared_symbol():
 def test_trace_kernel_id_is_the_build_source_hash():
     """The library reports the identity build.py hashed from the trace kernel's sources (the guard
     of every stored PMC profile); an experiment macro gives another identity, a measurement-only
-    macro does not."""
+    macro does not.  The replay kernels' file is not part of it, so an edit there keeps the profiles."""
     from audiorenderingv2_amd import build
     kid = int(_lib.lib().arx_trace_kernel_id())
     assert kid != 0
     assert kid == int(build.trace_source_id()[:-3], 16)
+    assert "arx_replay.hip" not in build.TRACE_KERNEL_FILES
+    assert all(os.path.exists(os.path.join(build.CSRC, f)) for f in build.TRACE_KERNEL_FILES)
     assert build.trace_source_id(("ARX_TRACE_COUNT=1",)) == build.trace_source_id()
     assert build.trace_source_id(("ARX_TRACE_LEAFFLAT=1",)) != build.trace_source_id()
 
