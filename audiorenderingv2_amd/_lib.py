@@ -75,6 +75,17 @@ class ArxListenerResult(C.Structure):
 
 LISTENER_BATCHED, LISTENER_SINGLE = 0, 1  # ARX_LISTENER_*
 
+
+class ArxBandResult(C.Structure):
+    """arx_band_result (40 B, no implicit padding)."""
+    _fields_ = [
+        ("queries", C.c_uint64), ("receiver_hits", C.c_uint64), ("misses", C.c_uint64),
+        ("warm_launches", C.c_int32), ("reserved", C.c_int32), ("reserved2", C.c_uint64),
+    ]
+
+
+MAX_BANDS = 8  # ARX_MAX_BANDS
+
 # include/arx.h ARX_ACOUSTICS_C* (the level tests' f64 literals) and ARX_VALID_* (bit order)
 ACOUSTICS_LEVELS = {5: 3.1622776601683794e-01, 10: 1.0000000000000001e-01, 25: 3.1622776601683794e-03,
                     35: 3.1622776601683794e-04}
@@ -177,6 +188,11 @@ SIGNATURES = {
     "arx_debug_set_listener_chunk": (C.c_int, [_P, C.c_int32]),
     "arx_debug_listener_bytes": (C.c_uint64, [C.c_uint64, C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "arx_debug_listener_layout": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _I64]),
+    "arx_set_band_absorption": (C.c_int, [_P, _F, C.c_int32, C.c_int64]),
+    "arx_band_count": (C.c_int32, [_P]),
+    "arx_band_table_check": (C.c_int, [_F, _F, C.c_int32, C.c_int64, _I32, _I64]),
+    "arx_render_bands": (C.c_int, [_P, _P, _P, C.POINTER(ArxAcoustics), C.POINTER(ArxBandResult), _D]),
+    "arx_debug_band_bytes": (C.c_uint64, [C.c_int32, C.c_int64, C.c_int32]),
     "arx_debug_set_trace_path": (C.c_int, [_P, C.c_int]),
     "arx_debug_set_refit_pad": (C.c_int, [_P, C.c_float]),
     "arx_debug_check_tree_limits": (C.c_int, [C.c_uint64, C.c_uint64]),

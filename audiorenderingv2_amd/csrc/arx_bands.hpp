@@ -1,0 +1,47 @@
+// arx_bands.hpp -- frequency-band absorption (arx_render_bands, include/arx.h): the arguments of
+// band_replay_kernel (arx_replay.hip) and the layout of the call's scratch.
+//
+// A band is the scene with another absorption per triangle.  A specular ray's geometry does not depend on
+// absorption, so one walk over a ray's recorded hits carries every band's energy into that band's own
+// histogram: the band arguments ride beside the TraceArgs of the replay as a second kernel parameter.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "arx_layout.hpp"
+
+namespace arx {
+
+constexpr int32_t kMaxBands = 8;         // ARX_MAX_BANDS
+constexpr int32_t kBandCounterWords = 8; // a band's counter block: [0] queries [1] receiver hits [2] misses, padding
+
+// The compiled width that serves n_bands: the device table's row, so a hit fetches its bands in one or
+// two 16-B loads.
+ARX_HOST_DEVICE inline int32_t band_width(int32_t n_bands) { return n_bands <= 4 ? 4 : 8; }
+
+struct BandArgs {
+    const float* table;            // [triangle][band_width(n_bands)] f32 absorption, by global triangle id; padding 0
+    unsigned long long* hist;      // band b's [L | R] histogram at hist + b * 2 * ir_len
+    unsigned long long* counters;  // band b's block at counters + b * kBandCounterWords
+    int64_t n_tris;                // rows of the table (the scene's input triangles), >= 1
+    int32_t n_bands;               // 1 .. kMaxBands
+    int32_t pad;
+};
+static_assert(sizeof(BandArgs) == 40, "BandArgs: a kernel parameter behind TraceArgs");
+
+// The scratch of a call for n_bands bands, as byte offsets (every region 16-B aligned): per band a
+// histogram, a counter block, three arx_acoustics and an f32 IR pair (the lefts, then the rights); then one
+// decay-curve buffer and the analysis kernels' scratch.
+struct BandScratchLayout {
+    uint64_t hist, counters, res, ir, edc, acou, total;
+};
+BandScratchLayout band_scratch_layout(int32_t ir_len, int32_t n_bands);
+
+// The frame of every band from launch_path_record's records (band_replay_kernel): a is the replay's
+// arguments (dirs and rec the cache's; its hist and counters are not used), with the clear of the bands'
+// histograms and counter blocks in front.  Band b's histogram and counters are those of
+// launch_path_replay on a scene whose triangles carry table[.][b].
+hipError_t launch_band_replay(const TraceArgs& a, const BandArgs& b, hipStream_t s);
+
+}  // namespace arx

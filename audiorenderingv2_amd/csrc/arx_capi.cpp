@@ -385,6 +385,7 @@ void arx_destroy(arx_renderer* r) {
     free_path_cache(r->path_cache);
     free_listener_batch(r->listeners);
     free_walk(r->walk);
+    free_bands(r->bands);
     if (r->h_tree_flag) hipHostFree(r->h_tree_flag);
     hipFree(r->d_conv_in);
     hipFree(r->d_conv_out);

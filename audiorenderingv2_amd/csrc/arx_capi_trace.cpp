@@ -19,13 +19,13 @@ using namespace arx;
 #define ARX_TRACE_PROF 0  // measurement builds only (build.py --exp TAG -D ARX_TRACE_PROF=1)
 #endif
 
-namespace {
-
-float initial_energy(const arx_config& c) {
+float arx::initial_energy(const arx_config& c) {
     // devicePrograms.cu:208 -- (x*y*z) is an int product in the reference
     const int32_t n = c.rays_x * c.rays_y * c.rays_z;
     return (float)((double)c.base_power / ((double)n * 4.18879020478));
 }
+
+namespace {
 
 // OptixModel.cpp:178-193 (glm::rotate(mat4(1), -radians(yaw), +Y) * v, then + camera),
 // restated with glm's exact operation order (matrix_transform.inl rotate, type_mat4x4.inl
@@ -578,12 +578,13 @@ arx_status arx::set_scene_image(arx_renderer* r, SceneRef img) {
     ++r->scene_gen;
     r->scene_dirty = true;
     r->recv_model_dirty = true;  // receiver ids and offsets follow the scene
+    r->bands.n_bands = 0;        // a band table belongs to the scene it was checked against
     return ARX_OK;
 }
 
 arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end, bool timed, bool clear,
                            ReplayProbe* probe) {
-    if (probe) probe->ready = false;
+    if (probe) probe->ready = probe->recorded = false;
     if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
     if (ray_end < ray_begin) return fail(ARX_ERR_INVALID_ARGUMENT, "ray_end < ray_begin");
     // global ray ids index the launch of N = x*y*z rays: energies are normalised by N and the
@@ -813,7 +814,9 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
         }
     }
     if (probe) {
-        probe->ready = replay && !record && pc.filter_on && pc.has_state && pc.d_filter && pc.rec_stream == r->stream;
+        probe->recorded = replay && !record && pc.rec_stream == r->stream;
+        probe->ready = probe->recorded && pc.filter_on && pc.has_state && pc.d_filter;
+        probe->state = pc.state;
         probe->args = a;
         probe->args.dirs = pc.d_dirs;
         probe->args.rec = pc.d_hits;

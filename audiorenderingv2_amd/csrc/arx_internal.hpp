@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/arx.h"
+#include "arx_bands.hpp"
 #include "arx_bvh.hpp"
 #include "arx_kernels.hpp"
 #include "arx_layout.hpp"
@@ -189,12 +190,31 @@ struct WalkScratch {
 constexpr int32_t kWalkTile = 8;      // items per MAC workgroup
 constexpr int32_t kWalkTileMax = 64;  // arx_debug_set_walk_tile
 void free_walk(WalkScratch& w);
-// What a replayed, filtered frame of the current key would launch, as trace_rays decides it (probe below).
+// Frequency-band absorption (arx_set_band_absorption / arx_render_bands, include/arx.h): the device table
+// ([triangle][band_width] f32, by global triangle id) and the call's scratch (band_scratch_layout,
+// arx_bands.hpp) -- one allocation each, kept across calls, freed when they must grow and at arx_destroy;
+// outside the path cache's cap.  arx_set_scene drops the table (n_bands 0) and keeps the memory.
+struct BandState {
+    int32_t n_bands = 0;          // 0: no table
+    int64_t n_tris = 0;           // the table's rows
+    float* d_table = nullptr;
+    uint64_t table_cap = 0;       // bytes of d_table
+    void* d_scratch = nullptr;
+    uint64_t scratch_cap = 0;     // bytes of d_scratch
+    void* h_pinned = nullptr;     // kMaxBands counter blocks, then kMaxBands x 3 arx_acoustics
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+};
+void free_bands(BandState& b);
+// What a replayed frame of the current key would launch, as trace_rays decides it (probe below).
 struct ReplayProbe {
-    bool ready = false;  // the key is recorded with its filter state, and this launch would only replay
-    TraceArgs args;      // the replay's arguments (dirs and rec the cache's)
+    bool ready = false;     // the key is recorded with its filter state, and this launch would only replay
+    bool recorded = false;  // the key is recorded (with or without filter state), and this launch would only replay
+    int32_t state = 0;      // what the launch would leave in PathCache::state had it run traced (kPath*)
+    TraceArgs args;         // the replay's arguments (dirs and rec the cache's)
     const void* planes = nullptr;
 };
+// Energy of a ray at the emitter (devicePrograms.cu:208).
+float initial_energy(const arx_config& c);
 
 // A ring of (start, end) event pairs around the last kTraceRing timed launches of one kind.  A launch
 // that is not timed records nothing and does not advance the ring.
@@ -298,6 +318,7 @@ struct arx_renderer {
     arx::PathCache path_cache;     // scene-only hits of the last repeated key (arx_debug_set_path_cache)
     arx::ListenerBatch listeners;  // arx_render_listeners' chunk scratch
     arx::WalkScratch walk;         // arx_convolute_walk's scratch
+    arx::BandState bands;          // arx_render_bands' table and scratch
     arx::QGrid qgrid{};
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)

@@ -2,7 +2,8 @@
 // (arx_trace.hip) and the receiver sub-tree alone.  replay_kernel replays every query of every ray
 // (the path cache); filter_kernel + replay_cand_kernel replay only the queries whose segment meets
 // the receiver's box (the path filter); filter_multi_kernel + cand_work_kernel +
-// replay_cand_multi_kernel do that for a chunk of listeners in one call.
+// replay_cand_multi_kernel do that for a chunk of listeners in one call; band_replay_kernel replays
+// every query once for several absorption tables (frequency bands).
 //
 // Every query here is the same arithmetic on the same bits as the traced frame's (the functions of
 // arx_trace_device.hpp), and each step the kernels share -- the kernel set-up, the record read, the
@@ -13,6 +14,7 @@
 
 #include <algorithm>
 
+#include "arx_bands.hpp"
 #include "arx_kernels.hpp"
 #include "arx_layout.hpp"
 #include "arx_trace_device.hpp"
@@ -179,6 +181,167 @@ __global__ __launch_bounds__(BLOCK) void replay_kernel(TraceArgs a) {
         }
     }
     flush_counters(a, n_q, n_rx, n_miss, lane);
+}
+
+// ------------------------------------------------------ frequency bands ---
+// arx_render_bands: NB bands answered by one walk over a ray's records.  A band is the scene with
+// another absorption per triangle (BandArgs::table, by global triangle id); absorption enters shade()
+// only through e = e * (1 - ab) and, via wants_query, through when e > energy_thres stops the ray.  So the
+// geometry of a query -- hit point, distance, chord, bin, reflection, next origin -- is run once, in
+// shade()'s operation order on the same bits, and only the energy is carried per band.
+//
+// band_shade is shade() for the recording's own ray (s, whose energy keeps following the scene's
+// absorption: the walk's loop guard) and for the bands in `alive`: a receiver half adds each live band's
+// energy to that band's [L | R] by shade()'s delay / hrtf / is_mono rules, a miss counts for each, anything
+// else multiplies e[b] by 1 - table[id][b].  A dead band's energy is still multiplied (no branch per
+// band); nothing reads it again.
+template <int NB>
+__device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& ba, const float4* __restrict__ tbase,
+                                           RayState& s, const Best& best, float (&e)[NB], uint32_t alive,
+                                           uint32_t& rx, uint32_t& miss) {
+    const int hit = best.unit;
+    if (hit < 0) {
+        miss |= alive;
+        s.depth = -1;
+        return;
+    }
+    const float4* tp = tbase + hit;
+    const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
+    const float3 P1 = make_float3(p0.x, p0.y, p0.z);
+    const float3 P2 = make_float3(p1.x, p1.y, p1.z);
+    const float3 P3 = make_float3(p2.x, p2.y, p2.z);
+    const float ab = p0.w;
+    const float3 U = sub3(P2, P1), V = sub3(P3, P1);
+    const float3 cr = make_float3(U.y * V.z - V.y * U.z, U.z * V.x - V.z * U.x, U.x * V.y - V.x * U.y);
+    const float hv = best.v, hw = best.w, hdet = best.det;
+    const float bu = hv / hdet;
+    const float bv = hw / hdet;
+    const float w0 = (1.0f - bu) - bv;
+    const float3 P = add3(add3(scale3(w0, P1), scale3(bu, P2)), scale3(bv, P3));
+    const float3 seg = sub3(P, s.pos);
+    s.dist += sqrtf(dot3(seg, seg));
+    float es = s.e;
+    if (ab < 0.0f) {  // receiver chord weighting: the chord once, every energy times it
+        const float3 center = make_float3(a.center[0], a.center[1], a.center[2]);
+        const float3 nd = scale3(1.0f / sqrtf(dot3(s.dir, s.dir)), s.dir);
+        const float3 oc = sub3(P, center);
+        const float qa = dot3(nd, nd);
+        const float qb = 2.0f * dot3(oc, nd);
+        const float qc = dot3(oc, oc) - 1.0f;
+        const float disc = qb * qb - (4.0f * qa) * qc;
+        if (disc <= 0.0f) {
+            es = 0.0f;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) e[b] = 0.0f;
+        } else {
+            const float sq = sqrtf(disc);
+            const float t1 = (-qb - sq) / (2.0f * qa);
+            const float t2 = (-qb + sq) / (2.0f * qa);
+            const float3 i1 = add3(P, scale3(t1, nd));
+            const float3 i2 = add3(P, scale3(t2, nd));
+            const float3 di = sub3(i1, i2);
+            const float chord = sqrtf(dot3(di, di));
+            es = es * chord;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) e[b] = e[b] * chord;
+        }
+    }
+    if (ab == -1.0f || ab == -2.0f) {  // receiver halves: every live band ends here
+        rx |= alive;
+        const int k = (int)roundf((s.dist / (float)kSpeedOfSound) * (float)a.sample_rate);
+        if (k < a.ir_len) {
+            const int kk = (k + a.delay < a.ir_len) ? k + a.delay : k;
+            const uint64_t own = (ab == -1.0f) ? 0u : (uint64_t)a.ir_len;
+            const uint64_t other = (ab == -1.0f) ? (uint64_t)a.ir_len : 0u;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                if ((alive >> b) & 1u) {  // alive holds bits below n_bands only: inside the bands' block
+                    unsigned long long* h = ba.hist + (uint64_t)b * 2u * (uint64_t)a.ir_len;
+                    hist_add(h + own, k, e[b], a.inv_unit);
+                    if (!a.is_mono) hist_add(h + other, kk, e[b] * (1.0f - a.hrtf), a.inv_unit);
+                }
+            }
+        }
+        s.depth = -1;
+    } else {  // specular reflection, and each band's own absorption
+        const float s2 = (2.0f * dot3(s.dir, cr)) / dot3(cr, cr);
+        s.dir = sub3(s.dir, scale3(s2, cr));
+        es = es * (1.0f - ab);
+        // a scene triangle: its id is below n_tris (the clamp keeps a bad record inside the table)
+        const uint64_t id = min((uint64_t)(uint32_t)best.id, (uint64_t)ba.n_tris - 1u);
+        const float4* __restrict__ row = reinterpret_cast<const float4*>(ba.table) + id * (NB / 4);
+        float tb[NB];
+#pragma unroll
+        for (int q = 0; q < NB / 4; ++q) {
+            const float4 t = row[q];
+            tb[4 * q + 0] = t.x;
+            tb[4 * q + 1] = t.y;
+            tb[4 * q + 2] = t.z;
+            tb[4 * q + 3] = t.w;
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) e[b] = e[b] * (1.0f - tb[b]);
+        ++s.depth;
+    }
+    s.e = es;
+    s.pos = add3(P, scale3(1e-3f, s.dir));
+}
+
+// band_replay_kernel, a lane per recorded slot on replay_kernel's plain grid.  The walk is the
+// recording's own loop (wants_query with the scene's energy); a band lives while its own loop guard
+// holds -- distance and depth are the walk's, so that is e[b] > energy_thres at every query -- and counts
+// queries only while it lives.  Every band's absorption is at least the scene's on every triangle
+// (arx_band_table_check), f32 1 - ab and the product by a non-negative e are monotone under rounding, so
+// e[b] never exceeds the recorded ray's energy at the same bounce: a live band's query always has a
+// record.  A lane leaves once no band lives.  Per band the histogram and the three counters are those of
+// replay_kernel on a scene that carries the band's absorption.
+template <int BLOCK, int NB>
+__global__ __launch_bounds__(BLOCK) void band_replay_kernel(TraceArgs a, BandArgs ba) {
+    static_assert(NB == 4 || NB == 8, "a table row is one or two 16-B loads");
+    const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a);
+    const int lane = threadIdx.x;
+    const uint64_t slot = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    float e[NB];
+    uint32_t n_q[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        e[b] = a.e0;
+        n_q[b] = 0u;
+    }
+    uint32_t alive = 0u, rx = 0u, miss = 0u;  // a bit per band
+    RayState s;
+    s.depth = -1;
+    bool active = false;
+    if (slot < c.n) {
+        ray_init(a, s, a.ray_begin + slot);
+        active = wants_query(a, s);
+        if (active) alive = (1u << min(ba.n_bands, NB)) - 1u;
+    }
+    Ray r;
+    Best best;
+    while (__ballot(active) != 0ull) {
+        if (active) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) alive &= (e[b] > a.energy_thres) ? ~0u : ~(1u << b);
+            active = alive != 0u;
+        }
+        if (active) {
+            load_record(c, (uint64_t)s.depth * c.n + slot, best);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) n_q[b] += (alive >> b) & 1u;
+        }
+        receiver_query(c, a, active, s, 0, r, best);
+        if (active) {
+            band_shade<NB>(a, ba, c.tbase, s, best, e, alive, rx, miss);
+            active = wants_query(a, s);
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if (b >= ba.n_bands) break;  // the same for every lane
+        a.counters = ba.counters + (uint64_t)b * kBandCounterWords;
+        flush_counters(a, n_q[b], (rx >> b) & 1u, (miss >> b) & 1u, lane);
+    }
 }
 
 // ------------------------------------------------------- the path filter ---
@@ -595,6 +758,24 @@ hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s) {
     constexpr int RB = ARX_REPLAY_BLOCK;
     const uint64_t n_rays = a.ray_end - a.ray_begin;
     hipLaunchKernelGGL(replay_kernel<RB>, dim3((unsigned)((n_rays + RB - 1) / RB)), dim3(RB), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_band_replay(const TraceArgs& a, const BandArgs& b, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.rec || !b.table || !b.hist || !b.counters || b.n_bands < 1 ||
+        b.n_bands > kMaxBands || b.n_tris < 1 || a.ir_len < 1 || a.ray_end <= a.ray_begin)
+        return hipErrorInvalidValue;
+    const hipError_t e = launch_clear(b.hist, (uint64_t)b.n_bands * 2 * (uint64_t)a.ir_len, b.counters,
+                                      b.n_bands * kBandCounterWords, s);
+    if (e != hipSuccess) return e;
+    constexpr int RB = ARX_REPLAY_BLOCK;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    const dim3 grid((unsigned)((n_rays + RB - 1) / RB));
+    if (band_width(b.n_bands) == 4)
+        hipLaunchKernelGGL((band_replay_kernel<RB, 4>), grid, dim3(RB), 0, s, a, b);
+    else
+        hipLaunchKernelGGL((band_replay_kernel<RB, 8>), grid, dim3(RB), 0, s, a, b);
     return hipGetLastError();
 }
 

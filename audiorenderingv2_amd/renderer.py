@@ -18,7 +18,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import ACOUSTICS_VALID, ArxAcoustics, ArxConfig, ArxListenerPose, ArxListenerResult, ArxStats, check, fptr, lib
+from ._lib import ACOUSTICS_VALID, MAX_BANDS, ArxAcoustics, ArxBandResult, ArxConfig, ArxListenerPose, ArxListenerResult, ArxStats, check, fptr, lib
 from .formats import write_float_lines
 from .scene import Scene
 
@@ -114,6 +114,24 @@ class AudioRenderer:
         self._scene_v = np.ascontiguousarray(scene.tri_v, np.float32)
         self._scene_a = np.ascontiguousarray(scene.tri_abs, np.float32)
         check(lib().arx_set_scene(self._h, fptr(self._scene_v), fptr(self._scene_a), scene.n_tris))
+        if getattr(scene, "band_abs", None) is not None:
+            self.set_band_absorption(scene.band_abs)
+
+    def set_band_absorption(self, table) -> None:
+        """arx_set_band_absorption: table (B, T) f32, band b's absorption of scene triangle t -- at least the
+        scene's own on every triangle, in [0, 1], a receiver mark kept; None or B == 0 drops it."""
+        if table is None:
+            check(lib().arx_set_band_absorption(self._h, None, 0, 0))
+            return
+        t = np.ascontiguousarray(table, np.float32)
+        if t.ndim != 2:
+            raise ValueError("band table: (bands, triangles)")
+        check(lib().arx_set_band_absorption(self._h, fptr(t), t.shape[0], t.shape[1]))
+
+    @property
+    def n_bands(self) -> int:
+        """arx_band_count: the bands of the installed table, 0 without one -- what render_bands returns."""
+        return int(lib().arx_band_count(self._h))
 
     def set_receiver_model(self, left: np.ndarray, right: np.ndarray) -> None:
         for side, t in enumerate((left, right)):
@@ -278,6 +296,33 @@ class AudioRenderer:
         check(lib().arx_render_listeners(self.handle, P.ctypes.data_as(C.POINTER(ArxListenerPose)), k, pl, pr, ac, res,
                                          C.byref(ms)))
         stats = np.frombuffer(res, dtype=LISTENER_RESULT_DTYPE, count=k).copy() if k else np.zeros(0, LISTENER_RESULT_DTYPE)
+        out_ac = None
+        if acoustics:
+            out_ac = [{name: _acoustics_dict(ac[3 * j + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)} for j in range(k)]
+        return {"ir": ir, "acoustics": out_ac, "stats": stats, "ms": float(ms.value)}
+
+    def render_bands(self, irs: bool | tuple = False, acoustics: bool = True) -> dict:
+        """arx_render_bands: every band of set_band_absorption's table from one walk over the recorded
+        paths, band b bit for bit the frame of a renderer whose scene carries table[b].  irs: False, True
+        (host arrays) or a pair of DeviceBuffers / device pointers of B * ir_len floats each (returned as
+        given).  Returns {"ir": (L[B, ir_len], R[B, ir_len]) | None, "acoustics": [{"left", "right",
+        "sum"}] * B | None, "stats": a structured array of arx_band_result's fields, "ms": the call's
+        device time}."""
+        k = self.n_bands  # the library's own count: the output buffers are sized from it
+        n = self.ir_length
+        ir = None
+        pl = pr = None
+        if irs is True:
+            ir = (np.zeros((k, n), np.float32), np.zeros((k, n), np.float32))
+            pl, pr = ir[0].ctypes.data, ir[1].ctypes.data
+        elif irs:
+            ir = tuple(irs)
+            pl, pr = (int(getattr(b, "ptr", b)) for b in ir)
+        ac = (ArxAcoustics * (3 * MAX_BANDS))() if acoustics else None
+        res = (ArxBandResult * MAX_BANDS)()
+        ms = C.c_double(0.0)
+        check(lib().arx_render_bands(self.handle, pl, pr, ac, res, C.byref(ms)))
+        stats = np.frombuffer(res, dtype=BAND_RESULT_DTYPE, count=k).copy()
         out_ac = None
         if acoustics:
             out_ac = [{name: _acoustics_dict(ac[3 * j + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)} for j in range(k)]
@@ -591,6 +636,22 @@ def _json_plain(v):
 
 LISTENER_RESULT_DTYPE = np.dtype([("queries", "<u8"), ("receiver_hits", "<u8"), ("misses", "<u8"), ("candidate_rays", "<u8"),
                                   ("route", "<i4"), ("reserved", "<i4"), ("reserved2", "<u8")])
+
+
+BAND_RESULT_DTYPE = np.dtype([("queries", "<u8"), ("receiver_hits", "<u8"), ("misses", "<u8"), ("warm_launches", "<i4"),
+                              ("reserved", "<i4"), ("reserved2", "<u8")])  # arx_band_result
+
+
+def write_band_acoustics_json(path: str, bands_hz, acoustics: list) -> None:
+    """render_bands' acoustics as JSON: a list of {"band_hz", "left", "right", "sum"}, the channels as
+    write_acoustics_json writes them."""
+    if len(bands_hz) != len(acoustics):
+        raise ValueError(f"{len(bands_hz)} bands, {len(acoustics)} results")
+    out = [{"band_hz": float(hz), **{ch: {k: _json_plain(v) for k, v in vals.items()} for ch, vals in a.items()}}
+           for hz, a in zip(bands_hz, acoustics)]
+    with open(path, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
 
 
 def listener_grid(lo, hi, nx: int, nz: int, y: float, yaw_deg: float = 0.0) -> np.ndarray:

@@ -35,6 +35,7 @@ class Scene:
     tri_v: np.ndarray    # (T, 9) f32, P1 P2 P3
     tri_abs: np.ndarray  # (T,) f32
     names: list
+    band_abs: np.ndarray | None = None  # (B, T) f32 per-band absorption, every row >= tri_abs (arx_set_band_absorption)
 
     @property
     def n_tris(self) -> int:
@@ -54,6 +55,37 @@ def material_absorption(name: str, materials: dict[str, float] | list) -> float:
     return 0.5
 
 
+def material_bands(materials) -> int:
+    """Bands of a material list: 0 when every value is one coefficient, else the common length B of the
+    values that are sequences of per-band coefficients (a scalar beside them holds for every band)."""
+    items = materials.items() if isinstance(materials, dict) else materials
+    lens = {len(a) for _, a in items if np.ndim(a) == 1}
+    if len(lens) > 1 or any(np.ndim(a) > 1 for _, a in items):
+        raise ValueError(f"materials: per-band values of different lengths {sorted(lens)}")
+    return lens.pop() if lens else 0
+
+
+def material_band_absorption(name: str, materials, n_bands: int) -> np.ndarray:
+    """getMaterialAbsorption per band: (n_bands,) f32 -- the receiver marks and the 0.5 default in every
+    band, a scalar value in every band, a sequence as given."""
+    if name in ("receiver_left", "receiver_right"):
+        return np.full(n_bands, material_absorption(name, ()), np.float32)
+    items = materials.items() if isinstance(materials, dict) else materials
+    for n, a in items:
+        if n == name:
+            return np.broadcast_to(np.asarray(a, np.float32), (n_bands,)).copy()
+    return np.full(n_bands, 0.5, np.float32)
+
+
+def _banded(names, counts, materials, n_bands: int) -> tuple[np.ndarray, np.ndarray]:
+    """(tri_abs, band_abs) of triangles named names[i] x counts[i]: band_abs (B, T) from the materials,
+    tri_abs its minimum over the bands -- which always satisfies arx_set_band_absorption's rule (a
+    receiver mark is the same in every band, so it is its own minimum)."""
+    lut = {n: material_band_absorption(n, materials, n_bands) for n in set(names)}
+    band_abs = np.repeat(np.stack([lut[n] for n in names], 1), counts, axis=1).astype(np.float32)
+    return band_abs.min(axis=0), band_abs
+
+
 def load_meshes_npz(path: str) -> list[Mesh]:
     d = np.load(path)
     names = [str(x) for x in d["names"]]
@@ -61,14 +93,21 @@ def load_meshes_npz(path: str) -> list[Mesh]:
 
 
 def scene_from_meshes(meshes: list[Mesh], materials=()) -> Scene:
+    """Materials whose value is a sequence of B per-band coefficients give a scene with band_abs set and
+    tri_abs the per-triangle minimum over the bands."""
+    n_bands = material_bands(materials)
     tv, ab, names = [], [], []
     for m in meshes:
         t = m.triangles()
         tv.append(t)
-        ab.append(np.full(t.shape[0], material_absorption(m.name, materials), np.float32))
+        if not n_bands:
+            ab.append(np.full(t.shape[0], material_absorption(m.name, materials), np.float32))
         names.append(m.name)
     if not tv:
         return Scene(np.zeros((0, 9), np.float32), np.zeros(0, np.float32), [])
+    if n_bands:
+        tri_abs, band_abs = _banded(names, [t.shape[0] for t in tv], materials, n_bands)
+        return Scene(np.concatenate(tv), tri_abs, names, band_abs)
     return Scene(np.concatenate(tv), np.concatenate(ab), names)
 
 
@@ -186,6 +225,10 @@ def conference_standin(seed: int = 42, n_boxes: int = 400, n_cylinders: int = 25
     names = [mat_names[0]] * 12 + [mat_names[i] for i in np.repeat(box_mats, 12)] + \
             [mat_names[i] for i in np.repeat(cyl_mats, 128)]
     tri_v = np.concatenate([room, boxes, cyl]).astype(np.float32)
+    n_bands = material_bands(materials)
+    if n_bands:  # per-band materials: the scene's absorption is the minimum over the bands
+        tri_abs, band_abs = _banded(names, np.ones(len(names), np.int64), materials, n_bands)
+        return Scene(tri_v, tri_abs, names, band_abs)
     lut = {n: material_absorption(n, materials) for n in mat_names}
     tri_abs = np.array([lut[n] for n in names], np.float32)
     return Scene(tri_v, tri_abs, names)

@@ -725,6 +725,89 @@ uint64_t arx_debug_listener_bytes(uint64_t n_rays, int32_t ir_len, int64_t recv_
 arx_status arx_debug_listener_layout(int64_t n_scene_nodes, int64_t n_scene_tris, int64_t recv_nodes, int64_t recv_tris,
                                      int32_t listeners, int32_t slot, int64_t out5[5]);
 
+/* Frequency-band absorption: every band's frame from one recorded path set, in one call.
+ *
+ * Real materials absorb differently per octave band, and ISO 3382-1 reports its parameters per band.  A
+ * band is the scene with another absorption per triangle.  A specular ray's geometry does not depend on
+ * absorption, which enters a frame only as e = e * (1 - ab) at every reflection and through when
+ * e > energy_thres stops the ray; and the path cache keeps the scene-only closest hit of every query of
+ * every ray.  So one kernel walks each ray's records once, runs the receiver query once per bounce and
+ * carries one energy per band into that band's own histogram: all bands for about the price of one
+ * unfiltered replayed frame, with no scene build per band.
+ *
+ * Contract: band b's outputs are bit for bit those of a renderer whose scene is the same triangles with
+ * table[b] as absorption, every other setting and the listener equal, after arx_render and arx_analyze_ir:
+ * both finalized IR channels (merged as arx_render merges them with is_mono), the three counters and the
+ * three arx_acoustics.
+ *
+ * The rule for the table (arx_band_table_check; arx_set_band_absorption checks it against the absorption
+ * the scene's triangle records carry): for every scene triangle t and band b, table[b * n_tris + t] >=
+ * the scene's absorption of t, and every value lies in [0, 1]; a triangle the scene marks -1 or -2 (its own
+ * receiver halves) carries the same mark in every band.  Then a band's energy never exceeds the recorded
+ * ray's at the same bounce (f32 1 - ab and the product by a non-negative e are monotone under rounding), so
+ * every query a band runs has a record.  A scene whose absorption is the minimum over its bands always
+ * satisfies it.  A violation, a NaN included, is ARX_ERR_INVALID_ARGUMENT and arx_last_error() names the
+ * band and the triangle; so are n_tris other than the scene's and n_bands outside [0, ARX_MAX_BANDS].
+ * n_bands 0 drops the table, and so does every arx_set_scene.  A call that fails with
+ * ARX_ERR_INVALID_ARGUMENT or ARX_ERR_NOT_READY changes nothing: a table installed before stays installed
+ * (a device error while the new table is uploaded drops it).
+ * arx_band_count reports the bands of the installed table (0: none), which is what arx_render_bands will
+ * write: size its output buffers from it.  The table is not part of any cache key: the records depend only
+ * on the scene's own absorption.
+ *
+ * arx_render_bands' outputs follow arx_render_listeners': ir_left / ir_right n_bands x ir_len floats each,
+ * host or device memory copied with hipMemcpyDefault on the renderer's stream (both NULL: no IRs; exactly
+ * one NULL is an error), acoustics n_bands x 3 (channel 0, 1, 2 per band; host memory; NULL: no analysis),
+ * results one per band (host memory; NULL: none), *ms the device time of the whole call, its warm launches
+ * included (a pair of events, recorded only when ms is given).  The call synchronises once, at its end.  Like
+ * arx_get_stats it then reads the tree's off-grid flag: if the receiver refit of a listener move put a box
+ * outside the quantization grid, the call returns ARX_ERR_INTERNAL instead of finished results.
+ *
+ * Where the frame comes from.  While the cache holds no recording of the current key, the call first runs
+ * ordinary arx_render launches of the current settings -- normally two, never more than three -- and
+ * reports their count in warm_launches.  There is NO traced fallback: if the cache cannot hold the launch
+ * (cache off; not cacheable: global stack, CW4, f32 nodes; records over arx_debug_set_path_cache's
+ * max_bytes, or no room for them on the device) the call returns ARX_ERR_NOT_READY and the message says
+ * which -- raise max_bytes to at least arx_debug_path_cache_bytes().  ARX_ERR_NOT_READY also without a
+ * scene or without a table.  ARX_ERR_INVALID_ARGUMENT: NULL r, more than one frame in flight, a caller's
+ * own stream (arx_set_stream), an attached histogram.  Only the 24-B records and the cache's direction copy
+ * are read: the path filter may be on or off.
+ *
+ * What the call leaves alone: the renderer's last frame (arx_copy_ir, arx_get_stats, arx_get_acoustics, the
+ * IR generation streams follow) is untouched when no warm launch ran, else it is the last warm launch's;
+ * the listener, the records and the path filter's state stay.
+ *
+ * Memory, OUTSIDE arx_debug_set_path_cache's max_bytes (arx_debug_band_bytes): the device table,
+ * n_tris x W x 4 B with W = 4 for up to four bands and 8 beyond (a hit fetches its bands in one or two 16-B
+ * loads), and one scratch allocation per renderer -- per band 16 x ir_len (histogram) + 64 (counter block)
+ * + 336 (three arx_acoustics) + 8 x ir_len (f32 IR pair) B, then one decay-curve buffer of 24 x ir_len B
+ * and the analysis kernels' scratch (arx_debug_band_bytes(0, 0, 1) - 400).  Both are kept across calls and
+ * freed when they must grow and at arx_destroy.
+ *
+ * Out of scope: a filtered band replay (a candidate query's per-band energy needs the chain of earlier
+ * hits anyway, and per-band query counts need every ray); groups, the C++ shim and app.py modes; combining
+ * the band IRs into one broadband IR. */
+#define ARX_MAX_BANDS 8
+/* table[b * n_tris + t]: band b's absorption of scene triangle t (arx_set_scene's order). n_bands 0 drops it. */
+arx_status arx_set_band_absorption(arx_renderer* r, const float* table, int32_t n_bands, int64_t n_tris);
+/* bands of the installed table: 0 without one (and for a NULL r) */
+int32_t arx_band_count(const arx_renderer* r);
+/* host only: the rule above, checked; *bad_band / *bad_tri name the first offender (-1 / -1: none; either may be NULL) */
+arx_status arx_band_table_check(const float* scene_absorption, const float* table, int32_t n_bands,
+                                int64_t n_tris, int32_t* bad_band, int64_t* bad_tri);
+typedef struct arx_band_result {                                                         /* 40 B, no implicit padding */
+    uint64_t queries, receiver_hits, misses;   /* arx_stats' counters of this band's frame */
+    int32_t warm_launches;                     /* ordinary launches the call ran first to get a recording (same in every entry) */
+    int32_t reserved;                          /* 0 */
+    uint64_t reserved2;                        /* 0 */
+} arx_band_result;
+arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right,  /* n_bands*ir_len each, or both NULL */
+                            arx_acoustics* acoustics,                          /* n_bands*3, or NULL */
+                            arx_band_result* results,                          /* n_bands, or NULL */
+                            double* ms);                                       /* device time of the whole call, or NULL */
+/* host only: bytes of the table and the scratch above (0 for n_bands outside [1, ARX_MAX_BANDS]) */
+uint64_t arx_debug_band_bytes(int32_t ir_len, int64_t n_tris, int32_t n_bands);
+
 /* Walk-through convolution: one signal against a per-block IR schedule, in one call.
  *
  * ir_left / ir_right hold n_irs IRs of ir_len frames each (arx_render_listeners' layout; ir_len and the
