@@ -133,8 +133,8 @@ def test_short_file_and_ragged_tails(conference):
     rng = np.random.default_rng(9)
     for n_frames in (9000, 16000, 3 * 16000 + 5, 5 * 16000, 7 * 16000 + 15999):
         # a fresh IR on every member (the IR spectra are made with the first convolution after it, by
-        # the same fused pass as the one-GPU reference's; a file shorter than a block makes them in a
-        # pass of their own, whose rounding differs, and they are then kept)
+        # the same fused pass as the one-GPU reference's; a file shorter than a block makes them
+        # alone, by the same arithmetic and so to the same bits, and they are then kept)
         g.render()
         x = rng.standard_normal(n_frames).astype(np.float32)
         ref = one_gpu_conv(g.get_ir(), 16000, x)
