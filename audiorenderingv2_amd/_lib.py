@@ -85,6 +85,7 @@ class ArxBandResult(C.Structure):
 
 
 MAX_BANDS = 8  # ARX_MAX_BANDS
+BAND_TAPS_MAX = 8191  # ARX_BAND_TAPS_MAX
 
 # include/arx.h ARX_ACOUSTICS_C* (the level tests' f64 literals) and ARX_VALID_* (bit order)
 ACOUSTICS_LEVELS = {5: 3.1622776601683794e-01, 10: 1.0000000000000001e-01, 25: 3.1622776601683794e-03,
@@ -193,6 +194,9 @@ SIGNATURES = {
     "arx_band_table_check": (C.c_int, [_F, _F, C.c_int32, C.c_int64, _I32, _I64]),
     "arx_render_bands": (C.c_int, [_P, _P, _P, C.POINTER(ArxAcoustics), C.POINTER(ArxBandResult), _D]),
     "arx_debug_band_bytes": (C.c_uint64, [C.c_int32, C.c_int64, C.c_int32]),
+    "arx_band_filters": (C.c_int, [C.c_int32, _D, C.c_int32, C.c_int32, _D]),
+    "arx_combine_bands": (C.c_int, [_P, _P, _P, C.c_int32, C.c_size_t, _P, C.c_int32, _P, _P, _D]),
+    "arx_debug_combine_bytes": (C.c_uint64, [C.c_size_t, C.c_int32, C.c_int32]),
     "arx_debug_set_trace_path": (C.c_int, [_P, C.c_int]),
     "arx_debug_set_refit_pad": (C.c_int, [_P, C.c_float]),
     "arx_debug_check_tree_limits": (C.c_int, [C.c_uint64, C.c_uint64]),

@@ -25,7 +25,7 @@ OBJDIR = os.path.join(PKG, "_obj")
 LIB = os.path.join(PKG, "libarx.so")
 ARCH = os.environ.get("ARX_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["arx_trace.hip", "arx_replay.hip", "arx_receiver.hip", "arx_conv.hip", "arx_conv_stream.hip", "arx_conv_walk.hip", "arx_acoustics.hip", "arx_capi.cpp",
+SOURCES = ["arx_trace.hip", "arx_replay.hip", "arx_receiver.hip", "arx_conv.hip", "arx_conv_stream.hip", "arx_conv_walk.hip", "arx_band_synth.hip", "arx_acoustics.hip", "arx_capi.cpp",
            "arx_scene.cpp", "arx_capi_trace.cpp", "arx_capi_bands.cpp", "arx_capi_conv.cpp", "arx_group.cpp", "arx_bvh.cpp", "arx_io.cpp", "arx_wide.cpp"]
 # the file / live convolution's kernels and the FFT device code under them: the files conv_source_id hashes
 CONV_KERNEL_FILES = ("arx_conv_fft.hpp", "arx_conv_kernels.hpp")

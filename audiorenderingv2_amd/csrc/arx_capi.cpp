@@ -386,6 +386,7 @@ void arx_destroy(arx_renderer* r) {
     free_listener_batch(r->listeners);
     free_walk(r->walk);
     free_bands(r->bands);
+    free_synth(r->synth);
     if (r->h_tree_flag) hipHostFree(r->h_tree_flag);
     hipFree(r->d_conv_in);
     hipFree(r->d_conv_out);

@@ -1,6 +1,8 @@
 // arx_capi_bands.cpp -- frequency-band absorption behind the C ABI (include/arx.h): the band table and
 // its rule, and arx_render_bands -- every band's frame from one walk over the path cache's records
-// (band_replay_kernel, arx_replay.hip), each finalized and analysed as arx_render and arx_analyze_ir do it.
+// (band_replay_kernel, arx_replay.hip), each finalized and analysed as arx_render and arx_analyze_ir do it;
+// and band synthesis -- arx_band_filters' filter bank (host only) and arx_combine_bands, the band IRs
+// filtered and summed into one IR pair (band_synth_kernel, arx_band_synth.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,7 +45,38 @@ uint64_t band_table_bytes(int64_t n_tris, int32_t n_bands) {
     return (uint64_t)n_tris * (uint64_t)band_width(n_bands) * sizeof(float);
 }
 
+bool synth_taps_ok(int32_t taps) { return taps >= 1 && taps <= ARX_BAND_TAPS_MAX && (taps & 1) == 1; }
+
+// arx_combine_bands' scratch as byte offsets, every part rounded up to 256 B (include/arx.h's formula).
+struct SynthLayout {
+    uint64_t in_left, in_right, filters, out_left, out_right, total;
+};
+SynthLayout synth_layout(size_t ir_len, int32_t n_bands, int32_t taps) {
+    SynthLayout s;
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 255) & ~255ull;
+        return o;
+    };
+    const uint64_t B = (uint64_t)n_bands, L = (uint64_t)ir_len;
+    s.in_left = take(4 * B * L);
+    s.in_right = take(4 * B * L);
+    s.filters = take(8 * B * (uint64_t)taps);
+    s.out_left = take(4 * L);
+    s.out_right = take(4 * L);
+    s.total = at;
+    return s;
+}
+
 }  // namespace
+
+void arx::free_synth(SynthScratch& s) {
+    hipFree(s.d_scratch);
+    if (s.ev0) hipEventDestroy(s.ev0);
+    if (s.ev1) hipEventDestroy(s.ev1);
+    s = SynthScratch{};
+}
 
 BandScratchLayout arx::band_scratch_layout(int32_t ir_len, int32_t n_bands) {
     BandScratchLayout s;
@@ -274,6 +307,120 @@ int32_t arx_band_count(const arx_renderer* r) { return r ? r->bands.n_bands : 0;
 uint64_t arx_debug_band_bytes(int32_t ir_len, int64_t n_tris, int32_t n_bands) {
     if (ir_len < 0 || n_tris < 0 || n_bands < 1 || n_bands > kMaxBands) return 0;
     return band_table_bytes(n_tris, n_bands) + band_scratch_layout(ir_len, n_bands).total;
+}
+
+// ---- band synthesis (arx_band_synth.hip) ------------------------------------------------------------
+
+arx_status arx_band_filters(int32_t sample_rate, const double* crossovers_hz, int32_t n_bands, int32_t taps, double* g) {
+    if (!g) return fail(ARX_ERR_INVALID_ARGUMENT, "g is NULL");
+    if (n_bands < 1 || n_bands > kMaxBands) return fail(ARX_ERR_INVALID_ARGUMENT, "n_bands %d: 1..%d", n_bands, kMaxBands);
+    if (!synth_taps_ok(taps)) return fail(ARX_ERR_INVALID_ARGUMENT, "taps %d: odd, 1..%d", taps, ARX_BAND_TAPS_MAX);
+    if (sample_rate <= 0) return fail(ARX_ERR_INVALID_ARGUMENT, "sample rate %d: must be positive", sample_rate);
+    if (n_bands > 1 && !crossovers_hz) return fail(ARX_ERR_INVALID_ARGUMENT, "crossovers_hz is NULL");
+    for (int32_t i = 0; i + 1 < n_bands; ++i) {
+        const double x = crossovers_hz[i];
+        if (!std::isfinite(x) || x <= 0.0 || x >= 0.5 * (double)sample_rate || (i > 0 && !(x > crossovers_hz[i - 1])))
+            return fail(ARX_ERR_INVALID_ARGUMENT,
+                        "crossover %d (%g Hz): finite, positive, strictly ascending and below sample_rate / 2 = %g", i, x,
+                        0.5 * (double)sample_rate);
+    }
+    int64_t N = 1;
+    while (N < 4 * (int64_t)taps) N *= 2;
+    const int64_t H = N / 2, c = (taps - 1) / 2;
+    const double pi = 3.14159265358979323846;
+    std::vector<double> ct((size_t)N);  // cos(2 pi r / N)
+    for (int64_t r = 0; r < N; ++r) ct[(size_t)r] = std::cos(2.0 * pi * (double)r / (double)N);
+    // L_i on the grid, i = -1 .. n_bands-1, two rows at a time: G_b = L_b - L_(b-1), times w_m
+    std::vector<double> lo((size_t)H + 1, 0.0), hi((size_t)H + 1), G((size_t)H + 1);
+    std::vector<int64_t> support;
+    for (int32_t b = 0; b < n_bands; ++b) {
+        for (int64_t m = 0; m <= H; ++m) {
+            double L = 1.0;
+            if (b + 1 < n_bands && m > 0) {
+                const double u = std::log2((double)m * (double)sample_rate / (double)N / crossovers_hz[b]);
+                L = u <= -0.5 ? 1.0 : u >= 0.5 ? 0.0 : 0.5 * (1.0 - std::sin(pi * u));
+            }
+            hi[(size_t)m] = L;
+            G[(size_t)m] = ((m == 0 || m == H) ? 1.0 : 2.0) * (L - lo[(size_t)m]);
+        }
+        support.clear();  // outside the band G is zero, and a zero term leaves the sum as it is
+        for (int64_t m = 0; m <= H; ++m)
+            if (G[(size_t)m] != 0.0) support.push_back(m);
+        double* const gb = g + (size_t)b * (size_t)taps;
+        for (int64_t j = 0; j <= c; ++j) {
+            double sum = 0.0;
+            for (const int64_t m : support) sum += G[(size_t)m] * ct[(size_t)((m * j) & (N - 1))];
+            const double win = 0.5 * (1.0 + std::cos(pi * (double)j / (double)(c + 1)));
+            const double v = sum / (double)N * win;
+            gb[c + j] = v;
+            gb[c - j] = v;
+        }
+        lo.swap(hi);
+    }
+    return ARX_OK;
+}
+
+arx_status arx_combine_bands(arx_renderer* r, const float* ir_left, const float* ir_right, int32_t n_bands, size_t ir_len,
+                             const double* filters, int32_t taps, float* out_left, float* out_right, double* ms) {
+    if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
+    if (!ir_left || !ir_right || !filters || !out_left || !out_right) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_bands < 1 || n_bands > kMaxBands) return fail(ARX_ERR_INVALID_ARGUMENT, "n_bands %d: 1..%d", n_bands, kMaxBands);
+    if (!synth_taps_ok(taps)) return fail(ARX_ERR_INVALID_ARGUMENT, "taps %d: odd, 1..%d", taps, ARX_BAND_TAPS_MAX);
+    if (ir_len == 0 || ir_len > (size_t)INT32_MAX) return fail(ARX_ERR_INVALID_ARGUMENT, "ir_len %zu: 1..%d", ir_len, INT32_MAX);
+    if (r->stream != r->cur().stream) return fail(ARX_ERR_INVALID_ARGUMENT, "a band combine needs the renderer's own stream");
+    const SynthLayout lay = synth_layout(ir_len, n_bands, taps);
+    SynthScratch& sc = r->synth;
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    if (const arx_status wt = fif_wait_conv(r); wt != ARX_OK) return wt;
+    if (lay.total > sc.bytes) {  // nothing of an earlier call is in flight: every call ends synchronised
+        hipFree(sc.d_scratch);
+        sc.d_scratch = nullptr;
+        sc.bytes = 0;
+        if (hipMalloc(&sc.d_scratch, lay.total) != hipSuccess) {
+            (void)hipGetLastError();
+            sc.d_scratch = nullptr;
+            return fail(ARX_ERR_OUT_OF_MEMORY, "the band combine's scratch of %llu bytes", (unsigned long long)lay.total);
+        }
+        sc.bytes = lay.total;
+    }
+    char* const base = static_cast<char*>(sc.d_scratch);
+    const bool timed = r->timing || ms != nullptr;
+    if (timed) {
+        if (!sc.ev0) ARX_HIP(hipEventCreate(&sc.ev0));
+        if (!sc.ev1) ARX_HIP(hipEventCreate(&sc.ev1));
+        ARX_HIP(hipEventRecord(sc.ev0, r->stream));
+    }
+    BandSynthArgs a{};
+    a.ir_left = reinterpret_cast<const float*>(base + lay.in_left);
+    a.ir_right = reinterpret_cast<const float*>(base + lay.in_right);
+    a.filters = reinterpret_cast<const double*>(base + lay.filters);
+    a.out_left = reinterpret_cast<float*>(base + lay.out_left);
+    a.out_right = reinterpret_cast<float*>(base + lay.out_right);
+    a.ir_len = (int64_t)ir_len;
+    a.n_bands = n_bands;
+    a.taps = taps;
+    const size_t in_bytes = (size_t)n_bands * ir_len * sizeof(float), out_bytes = ir_len * sizeof(float);
+    ARX_HIP(hipMemcpyAsync(base + lay.in_left, ir_left, in_bytes, hipMemcpyDefault, r->stream));
+    ARX_HIP(hipMemcpyAsync(base + lay.in_right, ir_right, in_bytes, hipMemcpyDefault, r->stream));
+    ARX_HIP(hipMemcpyAsync(base + lay.filters, filters, (size_t)n_bands * (size_t)taps * sizeof(double), hipMemcpyDefault,
+                           r->stream));
+    ARX_HIP(launch_band_synth(a, r->stream));
+    ARX_HIP(hipMemcpyAsync(out_left, base + lay.out_left, out_bytes, hipMemcpyDefault, r->stream));
+    ARX_HIP(hipMemcpyAsync(out_right, base + lay.out_right, out_bytes, hipMemcpyDefault, r->stream));
+    if (timed) ARX_HIP(hipEventRecord(sc.ev1, r->stream));
+    if (const arx_status d = fif_done_conv(r); d != ARX_OK) return d;
+    ARX_HIP(hipStreamSynchronize(r->stream));
+    if (ms) {
+        float el = 0.0f;
+        ARX_HIP(hipEventElapsedTime(&el, sc.ev0, sc.ev1));
+        *ms = (double)el;
+    }
+    return ARX_OK;
+}
+
+uint64_t arx_debug_combine_bytes(size_t ir_len, int32_t n_bands, int32_t taps) {
+    if (ir_len == 0 || ir_len > (size_t)INT32_MAX || n_bands < 1 || n_bands > kMaxBands || !synth_taps_ok(taps)) return 0;
+    return synth_layout(ir_len, n_bands, taps).total;
 }
 
 }  // extern "C"

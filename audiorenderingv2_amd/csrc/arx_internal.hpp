@@ -205,6 +205,15 @@ struct BandState {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
 };
 void free_bands(BandState& b);
+// Band synthesis (arx_combine_bands, include/arx.h): one scratch allocation per renderer (the call's inputs,
+// filters and outputs), made by the first call, kept across calls and freed when it must grow and at
+// arx_destroy; outside the path cache's cap.
+struct SynthScratch {
+    void* d_scratch = nullptr;
+    uint64_t bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+};
+void free_synth(SynthScratch& s);
 // What a replayed frame of the current key would launch, as trace_rays decides it (probe below).
 struct ReplayProbe {
     bool ready = false;     // the key is recorded with its filter state, and this launch would only replay
@@ -319,6 +328,7 @@ struct arx_renderer {
     arx::ListenerBatch listeners;  // arx_render_listeners' chunk scratch
     arx::WalkScratch walk;         // arx_convolute_walk's scratch
     arx::BandState bands;          // arx_render_bands' table and scratch
+    arx::SynthScratch synth;       // arx_combine_bands' scratch
     arx::QGrid qgrid{};
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)

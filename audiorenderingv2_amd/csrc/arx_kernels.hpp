@@ -241,4 +241,20 @@ struct WalkArgs {
 // The five launches (IR spectra, forward, MAC, inverse, blend) on s; nothing waits on the host.
 hipError_t launch_walk(const WalkArgs& a, hipStream_t s);
 
+// ---- band synthesis (arx_band_synth.hip): one broadband IR pair from the band IRs ----
+// out[n] = (float) sum_b sum_k g_b[k] * ir_b[n + c - k], c = (taps - 1) / 2, in include/arx.h's order
+// (arx_combine_bands): per band one f64 accumulator, taps ascending, an explicit fma each; the bands' sums
+// added in band order; one rounding to f32.  Samples outside [0, ir_len) read as zero.
+struct BandSynthArgs {
+    const float* ir_left;    // n_bands x ir_len
+    const float* ir_right;
+    const double* filters;   // n_bands x taps
+    float* out_left;         // ir_len
+    float* out_right;
+    int64_t ir_len;          // 1 .. INT32_MAX
+    int32_t n_bands;         // 1 .. kMaxBands
+    int32_t taps;            // odd, 1 .. ARX_BAND_TAPS_MAX
+};
+hipError_t launch_band_synth(const BandSynthArgs& a, hipStream_t s);
+
 }  // namespace arx

@@ -328,6 +328,70 @@ class AudioRenderer:
             out_ac = [{name: _acoustics_dict(ac[3 * j + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)} for j in range(k)]
         return {"ir": ir, "acoustics": out_ac, "stats": stats, "ms": float(ms.value)}
 
+    def combine_bands(self, irs, filters, n_bands: int | None = None, ir_len: int | None = None, out=None,
+                      taps: int | None = None) -> dict:
+        """arx_combine_bands: one broadband IR pair from band IRs -- out = sum over the bands of filter b
+        convolved with IR b, zero-phase, in include/arx.h's f64 arithmetic, rounded once to f32.  irs: a
+        pair of [B, ir_len] float32 arrays, or a pair of DeviceBuffers / device pointers of B * ir_len floats
+        each with n_bands=B and ir_len (render_bands' irs).  filters: a [B, taps] array (converted to f64;
+        band_filters' result), or a DeviceBuffer / device pointer of B * taps doubles with taps.  out: None
+        (host arrays are returned) or a pair of DeviceBuffers / device pointers of ir_len floats each
+        (returned as given).  Needs no scene and leaves the renderer's own IR alone.  Returns {"ir": (L, R),
+        "ms": the call's device time}."""
+        keep = []  # host arrays the call reads
+        if n_bands is None:
+            L, R = (np.ascontiguousarray(a, np.float32) for a in irs)
+            if L.shape != R.shape or L.ndim != 2:
+                raise ValueError("irs: a pair of [B, ir_len] arrays")
+            keep += [L, R]
+            k, n, pl, pr = L.shape[0], L.shape[1], L.ctypes.data, R.ctypes.data
+        else:
+            if ir_len is None:
+                raise ValueError("device IRs need n_bands and ir_len")
+            k, n = int(n_bands), int(ir_len)
+            pl, pr = (int(getattr(b, "ptr", b)) for b in irs)
+        if taps is None:
+            g = np.ascontiguousarray(filters, np.float64)
+            if g.ndim != 2 or g.shape[0] != k:
+                raise ValueError(f"filters: a [{k}, taps] array")
+            keep.append(g)
+            t, pg = g.shape[1], g.ctypes.data
+        else:
+            t, pg = int(taps), int(getattr(filters, "ptr", filters))
+        host_out = None
+        if out is None:
+            host_out = (np.empty(n, np.float32), np.empty(n, np.float32))
+            ol, or_ = host_out[0].ctypes.data, host_out[1].ctypes.data
+        else:
+            out = tuple(out)
+            ol, or_ = (int(getattr(b, "ptr", b)) for b in out)
+        ms = C.c_double(0.0)
+        check(lib().arx_combine_bands(self.handle, pl or None, pr or None, k, n, pg or None, t, ol or None, or_ or None,
+                                      C.byref(ms)))
+        del keep
+        return {"ir": host_out if out is None else out, "ms": float(ms.value)}
+
+    def render_broadband(self, filters, set_ir: bool = False) -> dict:
+        """Frequency-dependent absorption made audible on the device: render_bands into device buffers, then
+        combine_bands on them with `filters` ([n_bands, taps], band_filters' result) -- the band IRs never
+        visit the host.  set_ir: the broadband IR becomes the renderer's IR (set_ir_device), so the next
+        convolution or stream block uses it.  Returns {"ir": (L, R) host arrays, "acoustics" and "stats":
+        render_bands', "render_ms": render_bands' device time, "ms": the combine's}."""
+        k, n = self.n_bands, self.ir_length
+        dev = self.settings.device
+        bufs = [DeviceBuffer(dev, max(k * n * 4, 4)) for _ in range(2)] + [DeviceBuffer(dev, max(n * 4, 4)) for _ in range(2)]
+        try:
+            rb = self.render_bands(irs=tuple(bufs[:2]), acoustics=True)
+            cb = self.combine_bands(tuple(bufs[:2]), filters, n_bands=k, ir_len=n, out=tuple(bufs[2:]))
+            ir = tuple(b.to_numpy(np.float32, n) for b in bufs[2:])
+            if set_ir:
+                self.set_ir_device(bufs[2].ptr, bufs[3].ptr)
+                check(lib().arx_copy_ir(self._h, None, None, n))  # the copy has left the buffers before they go
+        finally:
+            for b in bufs:
+                b.close()
+        return {"ir": ir, "acoustics": rb["acoustics"], "stats": rb["stats"], "render_ms": rb["ms"], "ms": cb["ms"]}
+
     def set_walk_tile(self, items: int) -> None:
         """arx_debug_set_walk_tile: items per multiply-accumulate workgroup of convolute_walk (0: the
         product's tile, else 1..64); the same bits either way."""
@@ -652,6 +716,25 @@ def write_band_acoustics_json(path: str, bands_hz, acoustics: list) -> None:
     with open(path, "w") as fh:
         json.dump(out, fh, indent=1)
         fh.write("\n")
+
+
+def octave_crossovers(centres_hz) -> np.ndarray:
+    """The crossover frequencies between neighbouring band centres: their geometric means (one fewer than
+    the centres), as band_filters takes them."""
+    f = np.asarray(centres_hz, np.float64).reshape(-1)
+    return np.sqrt(f[:-1] * f[1:])
+
+
+def band_filters(sample_rate: int, crossovers_hz, taps: int) -> np.ndarray:
+    """arx_band_filters (host only): the float64 [B, taps] linear-phase filter bank of B = len(crossovers_hz)
+    + 1 bands -- raised-cosine band edges one octave wide in log-frequency, Hann-windowed, symmetric on bits,
+    summing to a unit impulse at (taps - 1) / 2 -- that combine_bands and render_broadband take."""
+    x = np.ascontiguousarray(crossovers_hz, np.float64).reshape(-1)
+    g = np.zeros((x.size + 1, max(int(taps), 0)), np.float64)
+    D = C.POINTER(C.c_double)
+    check(lib().arx_band_filters(int(sample_rate), x.ctypes.data_as(D) if x.size else None, x.size + 1, int(taps),
+                                 g.ctypes.data_as(D)))
+    return g
 
 
 def listener_grid(lo, hi, nx: int, nz: int, y: float, yaw_deg: float = 0.0) -> np.ndarray:

@@ -785,8 +785,7 @@ arx_status arx_debug_listener_layout(int64_t n_scene_nodes, int64_t n_scene_tris
  * freed when they must grow and at arx_destroy.
  *
  * Out of scope: a filtered band replay (a candidate query's per-band energy needs the chain of earlier
- * hits anyway, and per-band query counts need every ray); groups, the C++ shim and app.py modes; combining
- * the band IRs into one broadband IR. */
+ * hits anyway, and per-band query counts need every ray); groups, the C++ shim and app.py modes. */
 #define ARX_MAX_BANDS 8
 /* table[b * n_tris + t]: band b's absorption of scene triangle t (arx_set_scene's order). n_bands 0 drops it. */
 arx_status arx_set_band_absorption(arx_renderer* r, const float* table, int32_t n_bands, int64_t n_tris);
@@ -807,6 +806,79 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right,  /
                             double* ms);                                       /* device time of the whole call, or NULL */
 /* host only: bytes of the table and the scratch above (0 for n_bands outside [1, ARX_MAX_BANDS]) */
 uint64_t arx_debug_band_bytes(int32_t ir_len, int64_t n_tris, int32_t n_bands);
+
+/* Band synthesis: one broadband IR pair from the band IRs, on the device.
+ *
+ * arx_render_bands gives every band's IR; arx_set_ir_device, the file convolution, the streams and
+ * arx_convolute_walk take one IR pair.  arx_combine_bands is the step between them: each band's IR filtered
+ * with that band's FIR filter, the bands summed, one f32 IR pair written.  An IR here is the energy
+ * histogram used directly as convolution taps (the reference's semantics), and the combine is the linear map
+ * out = sum_b g_b (*) ir_b on those taps.  With equal bands and a bank that sums to a unit impulse the result
+ * is the single-band IR again.
+ *
+ * The arithmetic, fixed so that results can be compared on bits.  With c = (taps - 1) / 2, for each ear and
+ * each n in [0, ir_len):
+ *
+ *   for b in 0 .. n_bands-1:
+ *       acc_b = +0.0
+ *       for k in 0 .. taps-1, ascending:
+ *           m = n + c - k
+ *           if 0 <= m < ir_len: acc_b = fma(g_b[k], (double)ir_b[m], acc_b)      one f64 fma
+ *   s = acc_0; for b in 1 .. n_bands-1: s = s + acc_b
+ *   out[n] = (float)s                                                            one rounding to f32
+ *
+ * So the result is zero-phase: the filters' delay c is taken out, and samples outside [0, ir_len) read as
+ * zero.  (A zero input leaves acc_b's bits as they are -- acc_b is never -0.0 -- so the kernel feeds zeros
+ * for them and skips stretches that lie wholly outside.)  No band's sum is split over several accumulators
+ * and no order is changed.  The filters must be finite: that is the caller's duty and is not checked on the
+ * device.  Outputs that overlap inputs are undefined.
+ *
+ * arx_band_filters (host only) designs the one filter bank everyone gets: n_bands linear-phase FIR filters
+ * of `taps` coefficients whose sum is a unit impulse at c.  With N the smallest power of two >= 4 taps and
+ * the grid f_m = m sample_rate / N, m = 0 .. N/2: the low-pass of crossover x_i is L_i(0) = 1 and otherwise,
+ * with u = log2(f / x_i), 1 for u <= -1/2, 0 for u >= 1/2 and (1 - sin(pi u)) / 2 between -- a raised cosine
+ * one octave wide in log-frequency; L_-1 = 0, L_(n_bands-1) = 1 and G_b = L_b - L_(b-1), so G_b >= 0 and the
+ * G_b sum to 1.  For j = 0 .. c: h_b[j] = (1/N) sum_m w_m G_b(f_m) cos(2 pi r / N) with r = (m j) mod N in
+ * integers, w_0 = w_(N/2) = 1 and every other w_m = 2, m ascending; win[j] = (1 + cos(pi j / (c + 1))) / 2
+ * (Hann); g_b[c + j] = g_b[c - j] = h_b[j] win[j], one value stored twice.  ARX_ERR_INVALID_ARGUMENT: NULL
+ * g; NULL crossovers with n_bands > 1; n_bands outside [1, ARX_MAX_BANDS]; taps even or outside
+ * [1, ARX_BAND_TAPS_MAX]; sample_rate <= 0; a crossover that is not finite, not positive, not strictly
+ * ascending, or >= sample_rate / 2.
+ *
+ * arx_combine_bands follows arx_convolute_walk: it needs no scene; ir_left / ir_right (n_bands x ir_len
+ * floats each, arx_render_bands' layout; ir_len is the caller's, not the renderer's), filters (n_bands x taps
+ * doubles) and out_left / out_right (ir_len floats each) may each be host or device memory on the renderer's
+ * device and are copied with hipMemcpyDefault on the renderer's stream; the call orders itself on that
+ * stream, synchronises once, at its end, and reports in *ms its device time, copies included (a pair of
+ * events; recorded when ms is given or arx_set_timing is on).  It leaves the renderer's IR, its IR
+ * generation, its streams, its listener, its path cache and arx_render_bands' scratch alone.
+ * ARX_ERR_INVALID_ARGUMENT: NULL r, ir_left, ir_right, filters, out_left or out_right; n_bands outside
+ * [1, ARX_MAX_BANDS]; taps even or outside [1, ARX_BAND_TAPS_MAX]; ir_len 0 or above INT32_MAX; a caller's
+ * own stream (arx_set_stream), as in arx_render_bands.  ARX_ERR_OUT_OF_MEMORY when the scratch cannot be
+ * allocated; the renderer stays usable.
+ *
+ * Memory, OUTSIDE arx_debug_set_path_cache's max_bytes: one scratch allocation per renderer, made by the
+ * first call, kept across calls, freed when it must grow and at arx_destroy.  A call needs
+ * (arx_debug_combine_bytes), every term rounded up to a multiple of 256:
+ *   2 x (4 n_bands ir_len)   the band IRs, left and right
+ *   + 8 n_bands taps         the filters
+ *   + 2 x (4 ir_len)         the outputs, left and right
+ * (8 bands, 48 kHz x 2 s, 4095 taps: 7.2 MB.)
+ *
+ * Not offered: groups, the C++ shim, app.py modes, several IR sets per call (listeners x bands), filters
+ * longer than ARX_BAND_TAPS_MAX. */
+#define ARX_BAND_TAPS_MAX 8191
+/* host only: g[b * taps + k], band b's filter; crossovers_hz n_bands - 1 values, ascending (NULL with one band) */
+arx_status arx_band_filters(int32_t sample_rate, const double* crossovers_hz, int32_t n_bands, int32_t taps,
+                            double* g);
+arx_status arx_combine_bands(arx_renderer* r,
+                             const float* ir_left, const float* ir_right, /* n_bands x ir_len each */
+                             int32_t n_bands, size_t ir_len,
+                             const double* filters, int32_t taps,          /* n_bands x taps */
+                             float* out_left, float* out_right,           /* ir_len each */
+                             double* ms);                                 /* device time of the call, or NULL */
+/* host only: scratch bytes of a call by the formula above; 0 for arguments the call rejects */
+uint64_t arx_debug_combine_bytes(size_t ir_len, int32_t n_bands, int32_t taps);
 
 /* Walk-through convolution: one signal against a per-block IR schedule, in one call.
  *
