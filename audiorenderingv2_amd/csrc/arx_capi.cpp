@@ -1,7 +1,8 @@
 // arx_capi.cpp -- C ABI of libarx.so (include/arx.h): the renderer itself -- the error channel,
 // its lifecycle, the frame sets of frames in flight, the timing rings, the simple setters and
-// getters and the device helpers.  The scene image is in arx_scene.cpp, a frame in
-// arx_capi_trace.cpp, the convolution in arx_capi_conv.cpp.
+// getters and the device helpers.  The scene image is in arx_scene.cpp, the tree on the device in
+// arx_capi_device_scene.cpp, a frame in arx_capi_trace.cpp, the path cache in arx_capi_path_cache.cpp, a
+// batch of listeners in arx_capi_listeners.cpp, the convolution in arx_capi_conv.cpp.
 //
 // Host-side counterpart of R/prebuild/obj_raytracer/AudioRenderer.cpp, re-designed for HIP: one
 // stream per frame set, persistent device buffers (the reference cudaMallocs and frees inside every

@@ -164,13 +164,8 @@ arx_status arx_set_band_absorption(arx_renderer* r, const float* table, int32_t 
     ARX_HIP(hipSetDevice(r->cfg.device));
     bs.n_bands = 0;
     const uint64_t need = band_table_bytes(n_tris, n_bands);
-    if (need > bs.table_cap) {  // no call is in flight: every arx_render_bands ends synchronised
-        hipFree(bs.d_table);
-        bs.d_table = nullptr;
-        bs.table_cap = 0;
-        ARX_HIP(hipMalloc(&bs.d_table, need));
-        bs.table_cap = need;
-    }
+    if (need > bs.table_cap)  // no call is in flight: every arx_render_bands ends synchronised
+        if (const arx_status st = grow_device(&bs.d_table, &bs.table_cap, need, 0, 1); st != ARX_OK) return st;
     ARX_HIP(hipMemcpy(bs.d_table, rows.data(), need, hipMemcpyHostToDevice));
     bs.n_bands = n_bands;
     bs.n_tris = n_tris;
@@ -228,13 +223,7 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     unsigned long long* h_cnt = static_cast<unsigned long long*>(bs.h_pinned);
     arx_acoustics* h_res = reinterpret_cast<arx_acoustics*>(h_cnt + kMaxBands * kBandCounterWords);
     const BandScratchLayout sc = band_scratch_layout(r->ir_len, B);
-    if (sc.total > bs.scratch_cap) {
-        hipFree(bs.d_scratch);
-        bs.d_scratch = nullptr;
-        bs.scratch_cap = 0;
-        ARX_HIP(hipMalloc(&bs.d_scratch, sc.total));
-        bs.scratch_cap = sc.total;
-    }
+    if (sc.total > bs.scratch_cap && (st = grow_device(&bs.d_scratch, &bs.scratch_cap, sc.total, 0, 1)) != ARX_OK) return st;
     char* const base = static_cast<char*>(bs.d_scratch);
     unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(base + sc.hist);
     unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(base + sc.counters);
@@ -250,24 +239,16 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     ba.n_tris = bs.n_tris;
     ba.n_bands = B;
     ARX_HIP(launch_band_replay(probe.args, ba, r->stream));
-    const double unit = std::ldexp((double)initial_energy(r->cfg), -arx_frac_bits(N));
+    const double unit = ir_unit(r->cfg);
     for (int32_t b = 0; b < B; ++b) {
         const long long* h = reinterpret_cast<const long long*>(d_hist + (size_t)b * 2 * ir_len);
         if (ir_left)
             ARX_HIP(launch_finalize_ir(h, d_irl + (size_t)b * ir_len, d_irr + (size_t)b * ir_len, r->ir_len, unit,
                                        r->cfg.is_mono, r->stream));
-        if (acoustics) {
-            AcousticsArgs args{};
-            args.hist = h;
-            args.n = r->ir_len;
-            args.sample_rate = r->cfg.sample_rate;
-            args.unit = unit;
-            args.edc = reinterpret_cast<long long*>(base + sc.edc);
-            args.out = d_res + 3 * b;
-            args.scratch = base + sc.acou;
-            args.shape = r->scan_shape == 0 ? kScanDefault : r->scan_shape;
-            ARX_HIP(launch_acoustics(args, r->stream));
-        }
+        if (acoustics)
+            ARX_HIP(launch_acoustics(acoustics_args(r, h, reinterpret_cast<long long*>(base + sc.edc), d_res + 3 * b,
+                                                    base + sc.acou),
+                                     r->stream));
     }
     if (ir_left) {
         ARX_HIP(hipMemcpyAsync(ir_left, d_irl, (size_t)B * ir_len * sizeof(float), hipMemcpyDefault, r->stream));

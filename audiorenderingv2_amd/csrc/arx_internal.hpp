@@ -1,8 +1,9 @@
 // arx_internal.hpp -- libarx.so internals shared by the C ABI translation units
 // (arx_capi.cpp: one renderer's lifecycle, frame sets, timing rings and getters; arx_scene.cpp: the
-// host-only scene image; arx_capi_trace.cpp: a frame -- device scene, trace, finalize, analysis;
-// arx_capi_conv.cpp: the file, live, streaming and walk-through convolution; arx_group.cpp:
-// ray-sharded multi-GPU groups).
+// host-only scene image; arx_capi_device_scene.cpp: the tree on the device; arx_capi_trace.cpp: a frame --
+// trace, finalize, analysis; arx_capi_path_cache.cpp: the path cache's buffers and launches;
+// arx_capi_listeners.cpp: a batch of listeners; arx_capi_bands.cpp: frequency bands; arx_capi_conv.cpp: the
+// file, live, streaming and walk-through convolution; arx_group.cpp: ray-sharded multi-GPU groups).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,7 @@
 #include "arx_bvh.hpp"
 #include "arx_kernels.hpp"
 #include "arx_layout.hpp"
+#include "arx_path_plan.hpp"
 #include "arx_wide.hpp"
 
 namespace arx {
@@ -92,30 +94,19 @@ SceneRef deserialize_scene(const uint8_t* p, size_t n, const char** why);
 struct arx_renderer;
 struct arx_stream;
 namespace arx {
-// Everything that changes a ray's path or length, so the per-ray costs one launch measured order the
-// pool of the next: a frame set keeps its sorted direction buffer while this stays the same.  The
-// listener's position and yaw are deliberately not in it (a few percent of the rays touch the receiver).
-struct OrderKey {
-    uint64_t scene_gen, tree_hash, seed, ray_begin, ray_end;
-    float emitter[3];
-    float e0, energy_thres, hrtf, dist_limit;
-    uint32_t max_bounces, dyn_share;
-    int32_t is_mono, instance;
-};
 // The path cache (arx_debug_set_path_cache, include/arx.h): the scene-only closest hit of every query
 // of every ray of one key, recorded by the second consecutive launch of that key and replayed against
-// the receiver by the launches after it (trace_rays, arx_capi_trace.cpp).  The key is an OrderKey
-// without dyn_share and instance, valid for every 16-bit LDS-stack launch: the cache carries its own
-// copy of the direction buffer it was recorded on, so neither the pool's share nor a frame set's own
-// scatter order matters to it.  One per renderer, shared by its frame sets.
+// the receiver by the launches after it (plan_path_cache, arx_path_plan.hpp; issue_path_replay,
+// arx_capi_path_cache.cpp).  The key is an OrderKey (arx_path_plan.hpp) without dyn_share and instance,
+// valid for every 16-bit LDS-stack launch: the cache carries its own copy of the direction buffer it was
+// recorded on, so neither the pool's share nor a frame set's own scatter order matters to it.  One per
+// renderer, shared by its frame sets.
 #ifndef ARX_PATH_CACHE_DEFAULT
 #define ARX_PATH_CACHE_DEFAULT 1  // build.py --exp with 0: the cache-off library (A/B partner)
 #endif
 #ifndef ARX_PATH_FILTER_DEFAULT
 #define ARX_PATH_FILTER_DEFAULT 1  // build.py --exp with 0: every replay unfiltered (A/B partner)
 #endif
-constexpr int kPathOff = 0, kPathTraced = 1, kPathRecorded = 2, kPathReplayed = 3, kPathNotCacheable = 4,
-              kPathOverCap = 5;  // arx_debug_path_cache_state
 constexpr int kPathFrames = 3;    // arx_renderer::kMaxFrames
 struct PathCache {
     int32_t mode = ARX_PATH_CACHE_DEFAULT;
@@ -152,6 +143,53 @@ struct PathCache {
     uint64_t filter_rays = 0;         // ... over this many rays
 };
 void free_path_cache(PathCache& p);
+// The cache's buffers for a recording of n rays and `need` bytes of records: made at the first recording
+// and kept across keys; a buffer that must grow is freed once every frame set's stream is idle (a replay
+// of the key before may still read it).  *fits false: the device has no room for them (the cache is
+// optional: the caller traces the launch instead); what was freed stays freed.
+arx_status path_cache_reserve(arx_renderer* r, uint64_t n, uint64_t need, bool* fits);
+// The current frame set's candidate list for n rays; false: no room on the device (the error cleared;
+// that size is not tried again), and the frame replays unfiltered.
+bool path_filter_list_reserve(arx_renderer* r, uint64_t n);
+// The filter's margin (filter_kernel): kFilterMargin plus the slab test's own slack, 2^-18 of the
+// largest coordinate magnitude the grid spans (scene, emitter and receiver lie on it).
+float path_filter_grow(const QGrid& g);
+// A launch the cache serves, on the current stream: with `record` the recording first, then the replay
+// of n_launch rays with the launch's arguments a -- filtered where the filter's state allows it -- and
+// PathCache::state set to what ran.
+arx_status issue_path_replay(arx_renderer* r, const TraceArgs& a, bool record, uint64_t n_launch, int grid_cus);
+
+// A device buffer that must grow (mandatory): the old one freed, then room for count + slack elements;
+// *cap counts elements and is 0 while there is no buffer.  The caller has made sure nothing in flight
+// still uses the old buffer.  Two buffers of one capacity take one call each.
+template <class T, class Cap>
+arx_status grow_device(T** p, Cap* cap, size_t count, size_t slack, size_t elem_bytes) {
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    ARX_HIP(hipMalloc(p, (count + slack) * elem_bytes));
+    *cap = (Cap)(count + slack);
+    return ARX_OK;
+}
+// An optional buffer (the path cache, its filter, a batch's scratch) that must grow to `bytes`, which *cap
+// counts as `units`.  False: no room on the device -- the error cleared, the pointer null, *no_room the
+// size that did not fit; a size at or above *no_room is not tried.  Synchronisation as above.
+inline bool known_no_room(uint64_t no_room, uint64_t bytes) { return no_room > 0 && bytes >= no_room; }
+template <class T>
+bool grow_device_optional(T** p, uint64_t* cap, uint64_t units, uint64_t bytes, uint64_t* no_room) {
+    if (known_no_room(*no_room, bytes)) return false;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        *no_room = bytes;
+        return false;
+    }
+    *cap = units;
+    return true;
+}
 
 // A batch of listeners (arx_render_listeners, include/arx.h): the scratch of one chunk -- per listener a
 // candidate list with its heads, a table entry, a histogram, a counter block, a candidate tally, three
@@ -245,9 +283,38 @@ struct EventRing {
 // time); clear: the direction pre-pass zeroes the histogram and counters first (render() after
 // begin_frame, instead of arx_clear_histogram's launch)
 // probe: nothing is launched; the scene is brought up to date, the path cache's decision for this launch
-// is made as usual, and *probe says whether it is "replay, with filter state".
+// is made as usual (plan_path_cache) and *probe says whether it is "replay, with filter state".  Of the
+// cache's history a probe writes one thing: records of another key are dropped, as a launch would drop them.
 arx_status trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end, bool timed, bool clear = false,
                       ReplayProbe* probe = nullptr);
+// Seconds-free scale of the fixed-point histogram: one unit of it in energy (finalize, analysis).
+double ir_unit(const arx_config& c);
+// The analysis of one histogram (3 decay curves into edc, 3 results into out) with the renderer's settings.
+AcousticsArgs acoustics_args(const arx_renderer* r, const long long* hist, long long* edc, arx_acoustics* out, void* scratch);
+// The tree on the device brought up to date with the scene, the receiver model and the listener's pose
+// (arx_capi_device_scene.cpp): buffers, grid, uploads, re-quantization, the receiver's refit.
+arx_status ensure_device_scene(arx_renderer* r);
+// Rotation of a receiver at yaw_deg, row-major, exactly arx_place_receiver_vertices' floats.
+void receiver_rotation(float yaw_deg, float m[9]);
+// Box padding the refit kernel takes for a receiver at `centre` (arx_debug_set_refit_pad's when set).
+float refit_pad(const arx_renderer* r, const float centre[3]);
+// World-space bound of the receiver placed at `centre` (for the quantization grid): the refit path's ball
+// widened by the refit kernel's box padding (the padded boxes it quantizes must stay on the grid), or the
+// host-built sub-tree's root box (wherever `centre` is).
+void receiver_bound(const arx_renderer* r, const float centre[3], float lo[3], float hi[3], bool* empty);
+// Whether the emitter lies in that bound widened by `grow`: every ray would be a filter candidate at bounce 0.
+bool emitter_in_receiver_box(const arx_renderer* r, const float centre[3], float grow);
+// The refit kernels' arguments that do not depend on a pose: the receiver's local model, where it goes in
+// the tree's arrays, the grid and the quantized nodes, the off-grid flag of the current tree write.
+RefitArgs refit_args(const arx_renderer* r);
+// The grid grown once for a batch, as ensure_device_scene grows it for a walking listener: the new grid
+// spans the old one, the scene, the emitter and [ulo, uhi] with half the extent as margin, the top node and
+// the scene are re-quantized on the device, and the renderer's own receiver is refit for it by the next
+// ensure_device_scene.
+arx_status grow_grid_for(arx_renderer* r, const float ulo[3], const float uhi[3]);
+// The node and triangle arrays widened to hold a batch's slots: new buffers, what the old ones held copied
+// on the device.  False: no room (the error cleared; the arrays as they were).
+bool widen_tree_arrays(arx_renderer* r, size_t need_nodes, size_t need_tris);
 // arx_clear_histogram without its launch: with frames in flight, the next frame takes the next set
 arx_status begin_frame(arx_renderer* r);
 // Install a built scene (arx_set_scene's second half): uploaded at the next trace.
