@@ -84,6 +84,14 @@ class ArxBandResult(C.Structure):
     ]
 
 
+class ArxListenerBandResult(C.Structure):
+    """arx_listener_band_result (48 B, no implicit padding)."""
+    _fields_ = [
+        ("queries", C.c_uint64), ("receiver_hits", C.c_uint64), ("misses", C.c_uint64),
+        ("candidate_rays", C.c_uint64), ("route", C.c_int32), ("warm_launches", C.c_int32), ("reserved2", C.c_uint64),
+    ]
+
+
 MAX_BANDS = 8  # ARX_MAX_BANDS
 BAND_TAPS_MAX = 8191  # ARX_BAND_TAPS_MAX
 
@@ -197,6 +205,9 @@ SIGNATURES = {
     "arx_band_filters": (C.c_int, [C.c_int32, _D, C.c_int32, C.c_int32, _D]),
     "arx_combine_bands": (C.c_int, [_P, _P, _P, C.c_int32, C.c_size_t, _P, C.c_int32, _P, _P, _D]),
     "arx_debug_combine_bytes": (C.c_uint64, [C.c_size_t, C.c_int32, C.c_int32]),
+    "arx_render_listener_bands": (C.c_int, [_P, C.POINTER(ArxListenerPose), C.c_size_t, _P, _P, _P, C.c_int32, _P, _P,
+                                            C.POINTER(ArxAcoustics), C.POINTER(ArxListenerBandResult), _D]),
+    "arx_debug_listener_band_bytes": (C.c_uint64, [C.c_uint64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "arx_debug_set_trace_path": (C.c_int, [_P, C.c_int]),
     "arx_debug_set_refit_pad": (C.c_int, [_P, C.c_float]),
     "arx_debug_check_tree_limits": (C.c_int, [C.c_uint64, C.c_uint64]),

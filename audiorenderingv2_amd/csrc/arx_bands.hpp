@@ -44,4 +44,18 @@ BandScratchLayout band_scratch_layout(int32_t ir_len, int32_t n_bands);
 // launch_path_replay on a scene whose triangles carry table[.][b].
 hipError_t launch_band_replay(const TraceArgs& a, const BandArgs& b, hipStream_t s);
 
+// A batch of listeners per band (arx_render_listener_bands; band_base_kernel / band_cand_multi_kernel).
+// A listener's bands' block is BandArgs' layout behind its ListenerEntry: entry.hist the bands' histograms,
+// entry.counters the bands' counter blocks; entry.cand lies behind them.
+// launch_band_base, once per call: per ray the queries each band makes along the scene-only recording, a
+// byte per band packed into `counts` (8 B per ray), and their sums in b.counters (cleared first; band b's at
+// b.counters + b * kBandCounterWords).  f.planes is the recording's filter state; b.hist is not used.
+hipError_t launch_band_base(const TraceArgs& a, const FilterArgs& f, const BandArgs& b, void* counts, hipStream_t s);
+// launch_listeners_replay for every band at once: the same filter pass and work items, then the band chain
+// over the candidates and the chunk's query counts from b.counters (launch_band_base's block) and `counts`.
+// Per listener and band the results are launch_band_replay's at that listener.  No clear: the caller clears
+// the chunk's blocks.
+hipError_t launch_listener_bands_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
+                                        int32_t listeners, const BandArgs& b, const void* counts, hipStream_t s);
+
 }  // namespace arx

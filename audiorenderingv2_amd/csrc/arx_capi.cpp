@@ -388,6 +388,7 @@ void arx_destroy(arx_renderer* r) {
     free_walk(r->walk);
     free_bands(r->bands);
     free_synth(r->synth);
+    free_listener_bands(r->listener_bands);
     if (r->h_tree_flag) hipHostFree(r->h_tree_flag);
     hipFree(r->d_conv_in);
     hipFree(r->d_conv_out);

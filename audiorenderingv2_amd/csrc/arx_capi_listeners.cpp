@@ -19,8 +19,7 @@ constexpr uint64_t kListenerCounterWords = 16;  // a listener's block: kCounters
 
 // arx_debug_listener_bytes' per-listener terms (include/arx.h)
 uint64_t listener_bytes_each(uint64_t n, int32_t ir_len, int64_t recv_nodes, int64_t recv_tris) {
-    return (uint64_t)recv_nodes * (sizeof(BvhNode) + sizeof(QNode2)) + (uint64_t)recv_tris * sizeof(TriRec) +
-           (sizeof(BvhNode) + sizeof(QNode2)) + sizeof(ListenerEntry) + 16ull * (uint64_t)ir_len +
+    return listener_slot_bytes(recv_nodes, recv_tris) + sizeof(ListenerEntry) + 16ull * (uint64_t)ir_len +
            kListenerCounterWords * 8 + 3 * sizeof(arx_acoustics) + 8ull * (uint64_t)ir_len + path_filter_list_bytes(n) +
            4 * listener_work_words(n);
 }
@@ -111,7 +110,7 @@ struct ListenerCall {
     size_t first = 0;             // poses before it went through the warm-up
     ReplayProbe probe;
     int32_t chunk = 0;            // listeners per chunk
-    int64_t recv_nodes = 0, recv_tris = 0, own_nodes = 0, own_tris = 0;
+    ListenerSlots sl;             // the receiver slots behind the renderer's own tree; sl.chunk == chunk
     ListenerScratch sc{};
     char* d_base = nullptr;       // the chunk scratch, and in it the slots' histograms, counter blocks and IRs
     unsigned long long* d_hist = nullptr;
@@ -119,10 +118,6 @@ struct ListenerCall {
     float* d_irl = nullptr;
     float* d_irr = nullptr;
     float fgrow = 0.0f;           // the filter's margin on the grid the batch runs on
-
-    ListenerLayout layout(int32_t slot) const {
-        return listener_layout(own_nodes, own_tris, recv_nodes, recv_tris, chunk, slot, trace_node_cache());
-    }
 };
 
 // The one-listener route: the loop's own step, then its outputs queued on the stream.
@@ -165,27 +160,6 @@ arx_status warm_up(ListenerCall& c) {
     return ARX_OK;
 }
 
-// The extended tree must pass the kernels' offset limits and the structural check, slot by slot.
-bool slots_valid(const ListenerCall& c, const ListenerLayout& last) {
-    const arx_renderer* r = c.r;
-    if (check_buffer_offsets((size_t)last.total_nodes, (size_t)last.total_tris) != ARX_OK) return false;
-    std::vector<BvhNode> moved(r->recv.nodes);
-    for (int32_t s = 0; s < c.chunk; s += std::max(1, c.chunk - 1)) {  // the first and the last slot
-        const ListenerLayout l = c.layout(s);
-        const int32_t ns = (int32_t)(l.node_begin - (c.own_nodes - c.recv_nodes)), ts = (int32_t)(l.tri_begin - (c.own_tris - c.recv_tris));
-        for (size_t i = 0; i < moved.size(); ++i)
-            for (int k = 0; k < 2; ++k) {
-                const int32_t cnt = r->recv.nodes[i].d[2 + k];
-                moved[i].d[k] = r->recv.nodes[i].d[k] + (cnt == 0 ? ns : cnt > 0 ? ts : 0);
-            }
-        const char* why = "";
-        if (!validate_bvh_range(moved.data(), (size_t)l.node_begin, moved.size(), (size_t)last.total_nodes,
-                                (size_t)last.total_tris, &why))
-            return false;
-    }
-    return true;
-}
-
 // 2. the batched poses: grid, slots and scratch before the first launch; any "no" sends the rest through
 // the loop.  *batch: the poses from c.first on may be batched, c.chunk at a time.
 arx_status prepare_batch(ListenerCall& c, bool* batch) {
@@ -194,36 +168,23 @@ arx_status prepare_batch(ListenerCall& c, bool* batch) {
     arx_status st;
     *batch = c.first < c.n;
     if (*batch) {
-        // the union of the remaining poses' receiver bounds on the grid (grown once if need be)
-        float ulo[3] = {1e30f, 1e30f, 1e30f}, uhi[3] = {-1e30f, -1e30f, -1e30f};
-        for (size_t j = c.first; j < c.n; ++j) {
-            const float centre[3] = {c.poses[j].x, c.poses[j].y, c.poses[j].z};
-            float lo[3], hi[3];
-            bool empty = false;
-            receiver_bound(r, centre, lo, hi, &empty);
-            for (int k = 0; k < 3; ++k) {
-                ulo[k] = std::min(ulo[k], lo[k]);
-                uhi[k] = std::max(uhi[k], hi[k]);
-            }
-        }
-        if (!qgrid_contains(r->qgrid, ulo, uhi) && (st = grow_grid_for(r, ulo, uhi)) != ARX_OK) return st;
+        if ((st = listener_grid_for(r, c.poses, c.first, c.n)) != ARX_OK) return st;
     }
-    c.recv_nodes = (int64_t)r->recv.nodes.size();
-    c.recv_tris = (int64_t)r->recv.tris.size();
-    c.own_nodes = r->scene_img ? 1 + (int64_t)r->scene_img->bvh.nodes.size() + c.recv_nodes : 0;
-    c.own_tris = r->scene_img ? (int64_t)r->scene_img->bvh.tris.size() + c.recv_tris : 0;
+    c.sl = listener_slots(r);
     if (*batch) {
-        const uint64_t each = listener_bytes_each(c.N, r->ir_len, c.recv_nodes, c.recv_tris);
+        const uint64_t each = listener_bytes_each(c.N, r->ir_len, c.sl.recv_nodes, c.sl.recv_tris);
         c.chunk = lb.forced_chunk > 0 ? lb.forced_chunk : (int32_t)std::min<uint64_t>(kListenerChunkMax, kListenerBudget / each);
         c.chunk = (int32_t)std::min<size_t>((size_t)c.chunk, c.n - c.first);
         *batch = c.chunk >= 1;
     }
+    c.sl.chunk = c.chunk;
     if (*batch) {
-        const ListenerLayout last = c.layout(c.chunk - 1);
-        *batch = slots_valid(c, last) && widen_tree_arrays(r, (size_t)last.total_nodes, (size_t)last.total_tris) &&
+        const ListenerLayout last = c.sl.layout(c.chunk - 1);
+        *batch = listener_slots_valid(r, c.sl) && widen_tree_arrays(r, (size_t)last.total_nodes, (size_t)last.total_tris) &&
                  listener_scratch_reserve(r, c.N, c.chunk);
         c.chunk = std::min(c.chunk, std::max(lb.chunk, 0));
     }
+    if (c.chunk != c.sl.chunk) *batch = false;  // the slots were checked for the chunk asked for
     if (*batch) {
         // the arrays may have moved and the grid grown: the replay's arguments as they stand now
         if ((st = trace_rays(r, 0, c.N, false, false, &c.probe)) != ARX_OK) return st;
@@ -245,22 +206,11 @@ void select_batched(ListenerCall& c) {
     const arx_renderer* r = c.r;
     const ListenerScratch& sc = c.sc;
     for (size_t j = c.first; j < c.n; ++j) {
-        const float centre[3] = {c.poses[j].x, c.poses[j].y, c.poses[j].z};
-        float lo[3], hi[3];
-        bool empty = false;
-        receiver_bound(r, centre, lo, hi, &empty);
-        if (emitter_in_receiver_box(r, centre, 2.0f * c.fgrow) || !qgrid_contains(r->qgrid, lo, hi)) continue;
+        if (!listener_pose_batchable(r, c.poses[j], c.fgrow)) continue;
         const size_t b = c.batched.size();
         const int32_t slot = (int32_t)(b % (size_t)c.chunk);
-        const ListenerLayout l = c.layout(slot);
         ListenerEntry& e = c.pin.entries[b];
-        std::memset(&e, 0, sizeof(e));
-        for (int k = 0; k < 3; ++k) e.center[k] = centre[k];
-        e.top = (int32_t)l.top;
-        receiver_rotation(c.poses[j].yaw_deg, e.m);
-        e.pad = refit_pad(r, centre);
-        e.node_shift = (int32_t)(l.node_begin - (c.own_nodes - c.recv_nodes));
-        e.tri_shift = (int32_t)(l.tri_begin - (c.own_tris - c.recv_tris));
+        listener_entry_place(r, c.sl, slot, c.poses[j], &e);
         e.hist = c.d_hist + (size_t)slot * 2 * c.ir_len;
         e.counters = c.d_cnt + (size_t)slot * kListenerCounterWords;
         e.cand = e.counters + kCounters;
@@ -401,6 +351,87 @@ arx_status render_listeners(ListenerCall& c) {
 }
 
 }  // namespace
+
+// ---- what arx_render_listener_bands (arx_capi_listener_bands.cpp) shares with the call above ----
+
+uint64_t arx::listener_slot_bytes(int64_t recv_nodes, int64_t recv_tris) {
+    return (uint64_t)recv_nodes * (sizeof(BvhNode) + sizeof(QNode2)) + (uint64_t)recv_tris * sizeof(TriRec) +
+           (sizeof(BvhNode) + sizeof(QNode2));
+}
+
+ListenerLayout arx::ListenerSlots::layout(int32_t slot) const {
+    return listener_layout(own_nodes, own_tris, recv_nodes, recv_tris, chunk, slot, trace_node_cache());
+}
+
+ListenerSlots arx::listener_slots(const arx_renderer* r) {
+    ListenerSlots s;
+    s.recv_nodes = (int64_t)r->recv.nodes.size();
+    s.recv_tris = (int64_t)r->recv.tris.size();
+    s.own_nodes = r->scene_img ? 1 + (int64_t)r->scene_img->bvh.nodes.size() + s.recv_nodes : 0;
+    s.own_tris = r->scene_img ? (int64_t)r->scene_img->bvh.tris.size() + s.recv_tris : 0;
+    return s;
+}
+
+// the union of the poses' receiver bounds on the grid (grown once if need be)
+arx_status arx::listener_grid_for(arx_renderer* r, const arx_listener_pose* poses, size_t first, size_t n) {
+    float ulo[3] = {1e30f, 1e30f, 1e30f}, uhi[3] = {-1e30f, -1e30f, -1e30f};
+    for (size_t j = first; j < n; ++j) {
+        const float centre[3] = {poses[j].x, poses[j].y, poses[j].z};
+        float lo[3], hi[3];
+        bool empty = false;
+        receiver_bound(r, centre, lo, hi, &empty);
+        for (int k = 0; k < 3; ++k) {
+            ulo[k] = std::min(ulo[k], lo[k]);
+            uhi[k] = std::max(uhi[k], hi[k]);
+        }
+    }
+    if (!qgrid_contains(r->qgrid, ulo, uhi)) return grow_grid_for(r, ulo, uhi);
+    return ARX_OK;
+}
+
+// The extended tree must pass the kernels' offset limits and the structural check, slot by slot.
+bool arx::listener_slots_valid(const arx_renderer* r, const ListenerSlots& c) {
+    const ListenerLayout last = c.layout(c.chunk - 1);
+    if (check_buffer_offsets((size_t)last.total_nodes, (size_t)last.total_tris) != ARX_OK) return false;
+    std::vector<BvhNode> moved(r->recv.nodes);
+    for (int32_t s = 0; s < c.chunk; s += std::max(1, c.chunk - 1)) {  // the first and the last slot
+        const ListenerLayout l = c.layout(s);
+        const int32_t ns = (int32_t)(l.node_begin - (c.own_nodes - c.recv_nodes)), ts = (int32_t)(l.tri_begin - (c.own_tris - c.recv_tris));
+        for (size_t i = 0; i < moved.size(); ++i)
+            for (int k = 0; k < 2; ++k) {
+                const int32_t cnt = r->recv.nodes[i].d[2 + k];
+                moved[i].d[k] = r->recv.nodes[i].d[k] + (cnt == 0 ? ns : cnt > 0 ? ts : 0);
+            }
+        const char* why = "";
+        if (!validate_bvh_range(moved.data(), (size_t)l.node_begin, moved.size(), (size_t)last.total_nodes,
+                                (size_t)last.total_tris, &why))
+            return false;
+    }
+    return true;
+}
+
+// Not batched: a pose whose box holds the emitter (every ray a candidate), or one off the grid.
+bool arx::listener_pose_batchable(const arx_renderer* r, const arx_listener_pose& p, float fgrow) {
+    const float centre[3] = {p.x, p.y, p.z};
+    float lo[3], hi[3];
+    bool empty = false;
+    receiver_bound(r, centre, lo, hi, &empty);
+    return !emitter_in_receiver_box(r, centre, 2.0f * fgrow) && qgrid_contains(r->qgrid, lo, hi);
+}
+
+// A table entry's pose and slot: centre, top node, the refit's rotation, padding and shifts; its pointers zero.
+void arx::listener_entry_place(const arx_renderer* r, const ListenerSlots& s, int32_t slot, const arx_listener_pose& p,
+                               ListenerEntry* e) {
+    const float centre[3] = {p.x, p.y, p.z};
+    const ListenerLayout l = s.layout(slot);
+    std::memset(e, 0, sizeof(*e));
+    for (int k = 0; k < 3; ++k) e->center[k] = centre[k];
+    e->top = (int32_t)l.top;
+    receiver_rotation(p.yaw_deg, e->m);
+    e->pad = refit_pad(r, centre);
+    e->node_shift = (int32_t)(l.node_begin - (s.own_nodes - s.recv_nodes));
+    e->tri_shift = (int32_t)(l.tri_begin - (s.own_tris - s.recv_tris));
+}
 
 void arx::free_listener_batch(ListenerBatch& b) {
     hipFree(b.d_scratch);

@@ -2,7 +2,8 @@
 // (arx_capi.cpp: one renderer's lifecycle, frame sets, timing rings and getters; arx_scene.cpp: the
 // host-only scene image; arx_capi_device_scene.cpp: the tree on the device; arx_capi_trace.cpp: a frame --
 // trace, finalize, analysis; arx_capi_path_cache.cpp: the path cache's buffers and launches;
-// arx_capi_listeners.cpp: a batch of listeners; arx_capi_bands.cpp: frequency bands; arx_capi_conv.cpp: the
+// arx_capi_listeners.cpp: a batch of listeners; arx_capi_bands.cpp: frequency bands;
+// arx_capi_listener_bands.cpp: the bands of a batch of listeners; arx_capi_conv.cpp: the
 // file, live, streaming and walk-through convolution; arx_group.cpp: ray-sharded multi-GPU groups).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -211,6 +212,42 @@ struct ListenerBatch {
 };
 constexpr uint64_t kListenerBudget = 512ull << 20;  // scratch of an automatic chunk
 void free_listener_batch(ListenerBatch& b);
+// What a chunk of receiver slots is laid out from (arx_capi_listeners.cpp; shared with
+// arx_capi_listener_bands.cpp): the receiver's and the renderer's own tree sizes, and the chunk.
+struct ListenerSlots {
+    int64_t recv_nodes = 0, recv_tris = 0, own_nodes = 0, own_tris = 0;
+    int32_t chunk = 0;
+    ListenerLayout layout(int32_t slot) const;
+};
+ListenerSlots listener_slots(const arx_renderer* r);  // chunk left 0
+// bytes of one slot in the node and triangle arrays: its nodes (64-B and 32-B), triangle records and top node
+uint64_t listener_slot_bytes(int64_t recv_nodes, int64_t recv_tris);
+// The quantization grid grown once, if need be, to hold the receivers of poses [first, n).
+arx_status listener_grid_for(arx_renderer* r, const arx_listener_pose* poses, size_t first, size_t n);
+// The tree extended by s.chunk slots passes the kernels' offset limits and the structural check.
+bool listener_slots_valid(const arx_renderer* r, const ListenerSlots& s);
+// A pose the batched kernels take: the emitter outside its receiver box grown by the filter's margin
+// fgrow, and its receiver on the grid.
+bool listener_pose_batchable(const arx_renderer* r, const arx_listener_pose& p, float fgrow);
+// A table entry's pose and slot (centre, top node, the refit's rotation, padding and shifts); its pointers zeroed.
+void listener_entry_place(const arx_renderer* r, const ListenerSlots& s, int32_t slot, const arx_listener_pose& p,
+                          ListenerEntry* e);
+// A batch of listeners per band (arx_render_listener_bands, include/arx.h): one scratch allocation -- the
+// call's per-ray band counts and base counter block, then per listener of a chunk what ListenerBatch holds
+// with a bands' block for the histogram, the counters, the results and the IRs, and a broadband IR pair --
+// made by the first batched call, kept across calls, freed when it must grow and at arx_destroy; outside
+// the path cache's cap.  The chunk size is ListenerBatch::forced_chunk's or automatic.
+struct ListenerBandBatch {
+    void* d_scratch = nullptr;
+    uint64_t scratch_bytes = 0;
+    uint64_t no_room = 0;         // > 0: a scratch of this size did not fit on the device: not tried again
+    void* d_filters = nullptr;    // the call's filter bank (n_bands x taps f64)
+    uint64_t filters_cap = 0;     // bytes
+    void* h_pinned = nullptr;     // per listener of a call: its table entry, counter blocks and results
+    size_t h_bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+};
+void free_listener_bands(ListenerBandBatch& b);
 // The walk-through convolution (arx_convolute_walk, include/arx.h): one scratch allocation per renderer
 // (walk_layout, arx_kernels.hpp), made by the first call, kept across calls and freed when it must grow and
 // at arx_destroy; outside the path cache's cap.
@@ -396,6 +433,7 @@ struct arx_renderer {
     arx::WalkScratch walk;         // arx_convolute_walk's scratch
     arx::BandState bands;          // arx_render_bands' table and scratch
     arx::SynthScratch synth;       // arx_combine_bands' scratch
+    arx::ListenerBandBatch listener_bands;  // arx_render_listener_bands' scratch
     arx::QGrid qgrid{};
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)

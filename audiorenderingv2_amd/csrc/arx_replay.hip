@@ -3,7 +3,8 @@
 // (the path cache); filter_kernel + replay_cand_kernel replay only the queries whose segment meets
 // the receiver's box (the path filter); filter_multi_kernel + cand_work_kernel +
 // replay_cand_multi_kernel do that for a chunk of listeners in one call; band_replay_kernel replays
-// every query once for several absorption tables (frequency bands).
+// every query once for several absorption tables (frequency bands); band_base_kernel +
+// band_cand_multi_kernel do the chunk of listeners for every band at once.
 //
 // Every query here is the same arithmetic on the same bits as the traced frame's (the functions of
 // arx_trace_device.hpp), and each step the kernels share -- the kernel set-up, the record read, the
@@ -195,6 +196,25 @@ __global__ __launch_bounds__(BLOCK) void replay_kernel(TraceArgs a) {
 // energy to that band's [L | R] by shade()'s delay / hrtf / is_mono rules, a miss counts for each, anything
 // else multiplies e[b] by 1 - table[id][b].  A dead band's energy is still multiplied (no branch per
 // band); nothing reads it again.
+// A reflection's absorption per band: e[b] times 1 - table[id][b], the row in one or two 16-B loads.  id
+// is a scene triangle's, below n_tris (the clamp keeps a bad record inside the table).
+template <int NB>
+__device__ __forceinline__ void band_absorb(const BandArgs& ba, int tri_id, float (&e)[NB]) {
+    const uint64_t id = min((uint64_t)(uint32_t)tri_id, (uint64_t)ba.n_tris - 1u);
+    const float4* __restrict__ row = reinterpret_cast<const float4*>(ba.table) + id * (NB / 4);
+    float tb[NB];
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) {
+        const float4 t = row[q];
+        tb[4 * q + 0] = t.x;
+        tb[4 * q + 1] = t.y;
+        tb[4 * q + 2] = t.z;
+        tb[4 * q + 3] = t.w;
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) e[b] = e[b] * (1.0f - tb[b]);
+}
+
 template <int NB>
 __device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& ba, const float4* __restrict__ tbase,
                                            RayState& s, const Best& best, float (&e)[NB], uint32_t alive,
@@ -267,20 +287,7 @@ __device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& b
         const float s2 = (2.0f * dot3(s.dir, cr)) / dot3(cr, cr);
         s.dir = sub3(s.dir, scale3(s2, cr));
         es = es * (1.0f - ab);
-        // a scene triangle: its id is below n_tris (the clamp keeps a bad record inside the table)
-        const uint64_t id = min((uint64_t)(uint32_t)best.id, (uint64_t)ba.n_tris - 1u);
-        const float4* __restrict__ row = reinterpret_cast<const float4*>(ba.table) + id * (NB / 4);
-        float tb[NB];
-#pragma unroll
-        for (int q = 0; q < NB / 4; ++q) {
-            const float4 t = row[q];
-            tb[4 * q + 0] = t.x;
-            tb[4 * q + 1] = t.y;
-            tb[4 * q + 2] = t.z;
-            tb[4 * q + 3] = t.w;
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b) e[b] = e[b] * (1.0f - tb[b]);
+        band_absorb<NB>(ba, best.id, e);
         ++s.depth;
     }
     s.e = es;
@@ -745,6 +752,208 @@ __global__ __launch_bounds__(64) void replay_cand_multi_kernel(TraceArgs a, Filt
     flush_counters(a, n_q, n_rx, n_miss, lane);
 }
 
+// ------------------------------------------- a batch of listeners, per band ---
+// arx_render_listener_bands: the listener batch's filtered replay carrying band_replay_kernel's energies.
+// Two things a filtered band replay needs that a filtered frame does not, and where they come from:
+//   - A candidate query's energy per band is the product over the ray's earlier hits.  Those are the
+//     recorded triangle ids (a 16-B record load and one table row each: band_absorb); the position, distance
+//     and direction before the candidate query are in the filter's planes.  So a candidate ray is walked
+//     once from bounce 0 and only its candidate bounces run the receiver query (band_chain).
+//   - A band's query count needs every ray.  base_b(ray), the queries band b makes along the ray's scene-only
+//     recording, does not depend on the listener: band_base_kernel counts it once per call for every ray.  A
+//     ray that a listener's receiver ends at query k took max(0, base_b - (k + 1)) queries of band b away,
+//     and only a candidate ray can be ended; a flagged last query is the ray's last recorded query and cuts
+//     nothing.  So per (listener, band): queries = sum of base_b over all rays - sum of the cuts of the ended.
+//
+// band_base_kernel, a lane per recorded slot on the plain grid: the ray's records for queries 0 .. count - 1
+// (the meta word's count, clamped as the filter clamps it), the energies from a.e0 through band_absorb, a
+// band alive -- and counting -- exactly as in band_replay_kernel.  The ray's counts go out packed, a byte per
+// band (count <= 64), 8 B per ray; the sums go to the base counter block (ba.counters).
+template <int BLOCK, int NB>
+__global__ __launch_bounds__(BLOCK) void band_base_kernel(TraceArgs a, FilterArgs f, BandArgs ba, uint2* __restrict__ counts) {
+    static_assert(NB == 4 || NB == 8, "a table row is one or two 16-B loads");
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool have = gid < n;
+    const uint64_t slot = have ? gid : n - 1;  // n >= 1 (launch_band_base); idle lanes read in bounds
+    const float4* __restrict__ rec_hit = reinterpret_cast<const float4*>(a.rec);
+    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(
+        reinterpret_cast<const float4*>(f.planes) + (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+    const FilterRay fr = filter_ray_prelude(a, have, slot, meta);
+    float e[NB];
+    uint32_t n_q[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        e[b] = a.e0;
+        n_q[b] = 0u;
+    }
+    uint32_t alive = fr.count > 0u ? (1u << min(ba.n_bands, NB)) - 1u : 0u;
+    for (uint32_t q = 0; q < fr.count; ++q) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) alive &= (e[b] > a.energy_thres) ? ~0u : ~(1u << b);
+        if (alive == 0u) break;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) n_q[b] += (alive >> b) & 1u;
+        band_absorb<NB>(ba, __float_as_int(rec_hit[(uint64_t)q * n + slot].y), e);
+    }
+    if (have) {
+        uint32_t w[2] = {0u, 0u};
+#pragma unroll
+        for (int b = 0; b < NB; ++b) w[b >> 2] |= n_q[b] << (8 * (b & 3));  // n_q <= count <= 64
+        counts[slot] = make_uint2(w[0], w[1]);
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if (b >= ba.n_bands) break;  // the same for every lane
+        a.counters = ba.counters + (uint64_t)b * kBandCounterWords;
+        flush_counters(a, n_q[b], 0u, 0u, threadIdx.x);
+    }
+}
+
+// One entry of a listener's candidate list as a band chain (cand_chain's frame): the lane walks its ray's
+// bounces from 0.  Before every bounce `alive` is updated exactly as band_replay_kernel updates it; a bounce
+// outside the mask only multiplies the energies from the record's id; a bounce in the mask loads the stored
+// state and the record and runs cand_chain's query.  If the receiver gave the closest hit, or this is the
+// ray's flagged last query, band_shade runs into the listener's bands' block and the ray ends: its rx / miss
+// bits per live band, and per band the queries it took away, from the ray's packed counts.  A ray that does
+// not end contributes nothing, and nothing past its last candidate bounce is read.  Wave-wide like
+// receiver_query.
+template <int BLOCK, int NB>
+__device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const TraceArgs& a, const BandArgs& ba,
+                                           const FilterCand* __restrict__ list, uint64_t i, bool have, int top,
+                                           const uint2* __restrict__ counts, uint32_t (&cut)[NB], uint32_t& rx,
+                                           uint32_t& miss) {
+    const uint64_t n = c.n;
+    unsigned long long mask = 0ull;
+    uint64_t slot = 0;
+    uint32_t m = 0u;
+    if (have) {
+        const FilterCand e = list[i];
+        mask = e.mask;
+        slot = e.slot < n ? e.slot : n - 1;
+        m = c.meta[slot];
+    }
+    const uint32_t count = min(m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
+    mask &= count > 0u ? ((1ull << (count - 1u)) << 1) - 1ull : 0ull;  // bits of queries the ray ran
+    float e[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) e[b] = a.e0;
+    bool active = mask != 0ull;
+    uint32_t alive = active ? (1u << min(ba.n_bands, NB)) - 1u : 0u;
+    uint32_t q = 0u;  // the bounce the energies stand before
+    rx = 0u;
+    miss = 0u;
+    Ray r;
+    Best best;
+    while (__ballot(active) != 0ull) {
+        RayState s;
+        s.depth = -1;
+        int unit0 = -1;
+        if (active) {
+            const uint32_t target = (uint32_t)__builtin_ctzll(mask);
+            for (;;) {
+#pragma unroll
+                for (int b = 0; b < NB; ++b) alive &= (e[b] > a.energy_thres) ? ~0u : ~(1u << b);
+                if (alive == 0u || q >= target) break;
+                band_absorb<NB>(ba, __float_as_int(c.rec_hit[(uint64_t)q * n + slot].y), e);
+                ++q;
+            }
+            active = alive != 0u;
+        }
+        if (active) {
+            const uint64_t at = (uint64_t)q * n + slot;
+            const float4 sp = c.seg[at], sd = c.state[at];
+            load_record(c, at, best);
+            s.pos = make_float3(sp.x, sp.y, sp.z);
+            s.dist = sp.w;
+            s.dir = make_float3(sd.x, sd.y, sd.z);
+            s.e = sd.w;
+            s.depth = (int)q;
+            unit0 = best.unit;
+        }
+        receiver_query(c, a, active, s, top, r, best);
+        if (active) {
+            const bool flagged = q + 1u == count && (m & (kFilterMiss | kFilterMarked)) != 0u;
+            mask &= mask - 1ull;
+            if (best.unit != unit0 || flagged) {
+                band_shade<NB>(a, ba, c.tbase, s, best, e, alive, rx, miss);
+                const uint2 pk = counts[slot];
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    const uint32_t base = ((b < 4 ? pk.x : pk.y) >> (8 * (b & 3))) & 0xffu;
+                    cut[b] += base > q + 1u ? base - (q + 1u) : 0u;
+                }
+                active = false;
+            } else if (mask == 0ull) {
+                active = false;
+            } else {  // the record stands: the scene's triangle reflects
+                band_absorb<NB>(ba, best.id, e);
+                ++q;
+            }
+        }
+    }
+}
+
+// band_cand_multi_kernel is replay_cand_multi_kernel with band_chain for cand_chain: the listener from
+// blockIdx.y, its work items gridDim.x apart, the entry's values scalar; e.hist and e.counters are the
+// listener's bands' block (BandArgs' layout).  Per band the block leaves in counter word 0 the queries its
+// ended rays took away (band_cut_kernel turns them into the frame's count), in words 1 and 2 the frame's
+// receiver hits and misses.  rx and miss are a bit per ray and band: a ballot's population count, summed in
+// scalar registers, lane 0 handing the wave's sum to flush_counters.
+template <int NB>
+__global__ __launch_bounds__(64) void band_cand_multi_kernel(TraceArgs a, FilterArgs f, const ListenerEntry* __restrict__ tbl,
+                                                             BandArgs ba, const uint2* __restrict__ counts) {
+    static_assert(NB == 4 || NB == 8, "a table row is one or two 16-B loads");
+    constexpr int BLOCK = 64;
+    const ListenerEntry& e = tbl[blockIdx.y];
+    const uint64_t n = a.ray_end - a.ray_begin;
+    const uint64_t fblocks = (n + kFilterBlock - 1) / kFilterBlock;
+    const uint32_t n_items = min(e.work[0], (uint32_t)min(fblocks * (kFilterBlock / BLOCK), (uint64_t)0xffffffffu));
+    if (blockIdx.x >= n_items) return;
+    for (int k = 0; k < 3; ++k) a.center[k] = e.center[k];
+    ba.hist = e.hist;
+    ba.counters = e.counters;
+    const FilterCand* list = e.list;
+    const int top = e.top;
+    const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a, f);
+    const int lane = threadIdx.x;
+    uint32_t cut[NB], w_rx[NB], w_miss[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) cut[b] = w_rx[b] = w_miss[b] = 0u;
+    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const uint32_t word = e.work[4u + item];  // the same address for every lane, like the head
+        const uint64_t fb = min((uint64_t)(word >> 4), fblocks - 1);
+        const uint32_t base = (word & 15u) * BLOCK;
+        const uint4 head = reinterpret_cast<const uint4*>(e.heads)[fb];
+        const uint32_t n_cand = min(head.x, kFilterBlock);
+        if (base == 0u && lane == 0 && head.x) atomicAdd(e.cand, (unsigned long long)head.x);
+        const uint64_t i = fb * kFilterBlock + base + lane;
+        uint32_t rx, miss;
+        band_chain<BLOCK, NB>(c, a, ba, list, i, base + lane < n_cand && i < n, top, counts, cut, rx, miss);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            w_rx[b] += (uint32_t)__popcll(__ballot((rx >> b) & 1u));
+            w_miss[b] += (uint32_t)__popcll(__ballot((miss >> b) & 1u));
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if (b >= ba.n_bands) break;  // the same for every lane
+        a.counters = ba.counters + (uint64_t)b * kBandCounterWords;
+        flush_counters(a, cut[b], lane == 0 ? w_rx[b] : 0u, lane == 0 ? w_miss[b] : 0u, lane);
+    }
+}
+
+// A chunk's query counts finished, a thread per (listener, band): the band's base total less what the
+// listener's ended rays took away.
+__global__ __launch_bounds__(256) void band_cut_kernel(const ListenerEntry* __restrict__ tbl, const unsigned long long* __restrict__ base,
+                                                       int32_t n_bands, int32_t listeners) {
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= listeners * n_bands) return;
+    unsigned long long* c = tbl[t / n_bands].counters + (uint64_t)(t % n_bands) * kBandCounterWords;
+    c[0] = base[(uint64_t)(t % n_bands) * kBandCounterWords] - c[0];
+}
+
 }  // namespace
 
 hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s) {
@@ -799,9 +1008,9 @@ hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, 
     return hipGetLastError();
 }
 
-hipError_t launch_listeners_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
-                                   int32_t listeners, hipStream_t s) {
-    (void)hipGetLastError();
+// A chunk's filter pass and its work items; *per: the candidate launch's blocks per listener.
+static hipError_t launch_listeners_filter(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
+                                          int32_t listeners, hipStream_t s, uint64_t* per) {
     if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.rec || !a.cnodes || !f.planes || !d_table ||
         listeners < 1 || listeners > kListenerChunkMax || a.max_bounces < 1 || a.max_bounces > kFilterMaxBounces ||
         a.ray_end <= a.ray_begin)
@@ -817,8 +1026,53 @@ hipError_t launch_listeners_replay(const TraceArgs& a, const FilterArgs& f, cons
     // the candidates: each listener's work items, then a fixed number of blocks that walk them
     hipLaunchKernelGGL(cand_work_kernel, dim3((unsigned)listeners), dim3(1024), 0, s, d_table, (uint32_t)fblocks);
     constexpr uint64_t kCandBlocks = 8192;  // of one wave each: what the device holds at once, and a half more
-    const uint64_t per = std::min<uint64_t>(g2, (kCandBlocks + (uint64_t)listeners - 1) / (uint64_t)listeners);
+    *per = std::min<uint64_t>(g2, (kCandBlocks + (uint64_t)listeners - 1) / (uint64_t)listeners);
+    return hipSuccess;
+}
+
+hipError_t launch_listeners_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
+                                   int32_t listeners, hipStream_t s) {
+    (void)hipGetLastError();
+    uint64_t per = 0;
+    if (const hipError_t e = launch_listeners_filter(a, f, d_table, listeners, s, &per); e != hipSuccess) return e;
     hipLaunchKernelGGL(replay_cand_multi_kernel, dim3((unsigned)per, (unsigned)listeners), dim3(64), 0, s, a, f, d_table);
+    return hipGetLastError();
+}
+
+static bool band_args_ok(const BandArgs& b) {
+    return b.table && b.counters && b.n_bands >= 1 && b.n_bands <= kMaxBands && b.n_tris >= 1;
+}
+
+hipError_t launch_band_base(const TraceArgs& a, const FilterArgs& f, const BandArgs& b, void* counts, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!trace_can_cache(a, false) || !a.rec || !f.planes || !band_args_ok(b) || !counts || a.max_bounces < 1 ||
+        a.max_bounces > kFilterMaxBounces || a.ray_end <= a.ray_begin)
+        return hipErrorInvalidValue;
+    const hipError_t e = launch_clear(nullptr, 0, b.counters, b.n_bands * kBandCounterWords, s);
+    if (e != hipSuccess) return e;
+    constexpr int RB = ARX_REPLAY_BLOCK;
+    const uint64_t n_rays = a.ray_end - a.ray_begin;
+    const dim3 grid((unsigned)((n_rays + RB - 1) / RB));
+    if (band_width(b.n_bands) == 4)
+        hipLaunchKernelGGL((band_base_kernel<RB, 4>), grid, dim3(RB), 0, s, a, f, b, static_cast<uint2*>(counts));
+    else
+        hipLaunchKernelGGL((band_base_kernel<RB, 8>), grid, dim3(RB), 0, s, a, f, b, static_cast<uint2*>(counts));
+    return hipGetLastError();
+}
+
+hipError_t launch_listener_bands_replay(const TraceArgs& a, const FilterArgs& f, const ListenerEntry* d_table,
+                                        int32_t listeners, const BandArgs& b, const void* counts, hipStream_t s) {
+    (void)hipGetLastError();
+    if (!band_args_ok(b) || !counts) return hipErrorInvalidValue;
+    uint64_t per = 0;
+    if (const hipError_t e = launch_listeners_filter(a, f, d_table, listeners, s, &per); e != hipSuccess) return e;
+    const dim3 grid((unsigned)per, (unsigned)listeners);
+    if (band_width(b.n_bands) == 4)
+        hipLaunchKernelGGL((band_cand_multi_kernel<4>), grid, dim3(64), 0, s, a, f, d_table, b, static_cast<const uint2*>(counts));
+    else
+        hipLaunchKernelGGL((band_cand_multi_kernel<8>), grid, dim3(64), 0, s, a, f, d_table, b, static_cast<const uint2*>(counts));
+    hipLaunchKernelGGL(band_cut_kernel, dim3((unsigned)((listeners * b.n_bands + 255) / 256)), dim3(256), 0, s, d_table,
+                       b.counters, b.n_bands, listeners);
     return hipGetLastError();
 }
 

@@ -18,7 +18,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import ACOUSTICS_VALID, MAX_BANDS, ArxAcoustics, ArxBandResult, ArxConfig, ArxListenerPose, ArxListenerResult, ArxStats, check, fptr, lib
+from ._lib import ACOUSTICS_VALID, MAX_BANDS, ArxAcoustics, ArxBandResult, ArxConfig, ArxListenerBandResult, ArxListenerPose, ArxListenerResult, ArxStats, check, fptr, lib
 from .formats import write_float_lines
 from .scene import Scene
 
@@ -392,6 +392,86 @@ class AudioRenderer:
                 b.close()
         return {"ir": ir, "acoustics": rb["acoustics"], "stats": rb["stats"], "render_ms": rb["ms"], "ms": cb["ms"]}
 
+    def render_listener_bands(self, poses, irs: bool | tuple = False, acoustics: bool = True, filters=None,
+                              broadband: tuple | None = None) -> dict:
+        """arx_render_listener_bands: every band of set_band_absorption's table for a batch of listeners
+        (x, y, z, yaw_deg) from one recorded path set -- entry (j, b) bit for bit the loop of
+        setSphereCenterInOptix + render_bands (+ combine_bands) over the poses; the listener set before
+        stays.  irs: False, True (host arrays) or a pair of DeviceBuffers / device pointers of K * B * ir_len
+        floats each (returned as given).  filters: None, or a [B, taps] array (band_filters' result): then
+        every listener's bands are also combined into one broadband pair, into host arrays or, with
+        broadband=(left, right), into DeviceBuffers / device pointers of K * ir_len floats each
+        (convolute_walk's layout; returned as given).  Returns {"ir": (L[K, B, ir_len], R[K, B, ir_len]) |
+        None, "broadband": (L[K, ir_len], R[K, ir_len]) | None, "acoustics": [[{"left", "right", "sum"}] * B]
+        * K | None, "stats": a [K, B] structured array of arx_listener_band_result's fields, "ms": the
+        call's device time}."""
+        P = np.ascontiguousarray(poses, np.float32)
+        if P.ndim != 2 or P.shape[1] != 4:
+            raise ValueError("poses: a [K, 4] array of (x, y, z, yaw_deg)")
+        nb = self.n_bands  # the library's own count: the output buffers are sized from it
+        if broadband is not None and filters is None:
+            raise ValueError("broadband buffers need filters")
+        g = None
+        if filters is not None:
+            if nb < 1:
+                raise ValueError("filters need a band table (set_band_absorption)")
+            g = np.ascontiguousarray(filters, np.float64)
+            if g.ndim != 2 or g.shape[0] != nb:
+                raise ValueError(f"filters: a [{nb}, taps] array")
+        k, n = P.shape[0], self.ir_length
+        ir = bb = None
+        pl = pr = bl = br = None
+        if irs is True:
+            ir = (np.zeros((k, nb, n), np.float32), np.zeros((k, nb, n), np.float32))
+            pl, pr = ir[0].ctypes.data, ir[1].ctypes.data
+        elif irs:
+            ir = tuple(irs)
+            pl, pr = (int(getattr(b, "ptr", b)) for b in ir)
+        if g is not None:
+            if broadband is None:
+                bb = (np.zeros((k, n), np.float32), np.zeros((k, n), np.float32))
+                bl, br = bb[0].ctypes.data, bb[1].ctypes.data
+            else:
+                bb = tuple(broadband)
+                bl, br = (int(getattr(b, "ptr", b)) for b in bb)
+        cells = max(k * nb, 1)
+        ac = (ArxAcoustics * (3 * cells))() if acoustics else None
+        res = (ArxListenerBandResult * cells)()
+        ms = C.c_double(0.0)
+        check(lib().arx_render_listener_bands(self.handle, P.ctypes.data_as(C.POINTER(ArxListenerPose)), k, pl or None,
+                                              pr or None, g.ctypes.data if g is not None else None,
+                                              g.shape[1] if g is not None else 0, bl or None, br or None, ac, res,
+                                              C.byref(ms)))
+        stats = np.frombuffer(res, dtype=LISTENER_BAND_RESULT_DTYPE, count=k * nb).copy().reshape(k, nb)
+        out_ac = None
+        if acoustics:
+            out_ac = [[{name: _acoustics_dict(ac[3 * (j * nb + b) + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)}
+                       for b in range(nb)] for j in range(k)]
+        return {"ir": ir, "broadband": bb, "acoustics": out_ac, "stats": stats, "ms": float(ms.value)}
+
+    def auralise_walk_bands(self, poses, samples, filters, block_frames: int = 4096, crossfade_frames: int | None = None,
+                            fade: str | int = "hann") -> dict:
+        """auralise_walk with frequency-dependent absorption: render_listener_bands over the poses with the
+        broadband set in device buffers, the poses spread evenly over the input's blocks, then convolute_walk
+        on those buffers -- neither the band IRs nor the broadband IRs visit the host.  Returns
+        auralise_walk's dict."""
+        P = np.ascontiguousarray(poses, np.float32)
+        if P.ndim != 2 or P.shape[1] != 4:
+            raise ValueError("poses: a [K, 4] array of (x, y, z, yaw_deg)")
+        x = np.ascontiguousarray(samples, np.float64).reshape(-1)
+        B = int(block_frames)
+        F = B if crossfade_frames is None else int(crossfade_frames)
+        sched = walk_schedule(x.size, B, self.ir_length, P.shape[0])
+        dev = self.settings.device
+        bufs = [DeviceBuffer(dev, max(P.shape[0] * self.ir_length * 4, 4)) for _ in range(2)]
+        try:
+            rl = self.render_listener_bands(P, irs=False, acoustics=False, filters=filters, broadband=tuple(bufs))
+            res = self.convolute_walk(tuple(bufs), sched, x, B, F, fade, n_irs=P.shape[0])
+        finally:
+            for b in bufs:
+                b.close()
+        return {"out": res["out"], "ir_of_block": sched, "render_ms": rl["ms"], "ms": res["ms"]}
+
     def set_walk_tile(self, items: int) -> None:
         """arx_debug_set_walk_tile: items per multiply-accumulate workgroup of convolute_walk (0: the
         product's tile, else 1..64); the same bits either way."""
@@ -704,6 +784,29 @@ LISTENER_RESULT_DTYPE = np.dtype([("queries", "<u8"), ("receiver_hits", "<u8"), 
 
 BAND_RESULT_DTYPE = np.dtype([("queries", "<u8"), ("receiver_hits", "<u8"), ("misses", "<u8"), ("warm_launches", "<i4"),
                               ("reserved", "<i4"), ("reserved2", "<u8")])  # arx_band_result
+
+
+LISTENER_BAND_RESULT_DTYPE = np.dtype([("queries", "<u8"), ("receiver_hits", "<u8"), ("misses", "<u8"),
+                                       ("candidate_rays", "<u8"), ("route", "<i4"), ("warm_launches", "<i4"),
+                                       ("reserved2", "<u8")])  # arx_listener_band_result
+
+
+def write_band_acoustic_map_json(path: str, poses, bands_hz, acoustics: list) -> None:
+    """render_listener_bands' acoustics as JSON: [{"pose": [x, y, z, yaw_deg], "bands": [{"band_hz", "left",
+    "right", "sum"}]}] in pose order, each pose's bands as write_band_acoustics_json writes them."""
+    P = np.asarray(poses, np.float32).reshape(-1, 4)
+    if P.shape[0] != len(acoustics):
+        raise ValueError("one acoustics entry per pose")
+    out = []
+    for p, per_band in zip(P, acoustics):
+        if len(bands_hz) != len(per_band):
+            raise ValueError(f"{len(bands_hz)} bands, {len(per_band)} results")
+        out.append({"pose": [float(v) for v in p],
+                    "bands": [{"band_hz": float(hz), **{ch: {k: _json_plain(v) for k, v in vals.items()} for ch, vals in a.items()}}
+                              for hz, a in zip(bands_hz, per_band)]})
+    with open(path, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
 
 
 def write_band_acoustics_json(path: str, bands_hz, acoustics: list) -> None:

@@ -784,8 +784,9 @@ arx_status arx_debug_listener_layout(int64_t n_scene_nodes, int64_t n_scene_tris
  * and the analysis kernels' scratch (arx_debug_band_bytes(0, 0, 1) - 400).  Both are kept across calls and
  * freed when they must grow and at arx_destroy.
  *
- * Out of scope: a filtered band replay (a candidate query's per-band energy needs the chain of earlier
- * hits anyway, and per-band query counts need every ray); groups, the C++ shim and app.py modes. */
+ * This call's replay is unfiltered and serves the renderer's one listener; the filtered band replay, for a
+ * batch of listeners, is arx_render_listener_bands (below).  Out of scope: groups, the C++ shim and app.py
+ * modes. */
 #define ARX_MAX_BANDS 8
 /* table[b * n_tris + t]: band b's absorption of scene triangle t (arx_set_scene's order). n_bands 0 drops it. */
 arx_status arx_set_band_absorption(arx_renderer* r, const float* table, int32_t n_bands, int64_t n_tris);
@@ -865,8 +866,8 @@ uint64_t arx_debug_band_bytes(int32_t ir_len, int64_t n_tris, int32_t n_bands);
  *   + 2 x (4 ir_len)         the outputs, left and right
  * (8 bands, 48 kHz x 2 s, 4095 taps: 7.2 MB.)
  *
- * Not offered: groups, the C++ shim, app.py modes, several IR sets per call (listeners x bands), filters
- * longer than ARX_BAND_TAPS_MAX. */
+ * One IR set per call; several sets (listeners x bands) are combined inside arx_render_listener_bands
+ * (below).  Not offered: groups, the C++ shim, app.py modes, filters longer than ARX_BAND_TAPS_MAX. */
 #define ARX_BAND_TAPS_MAX 8191
 /* host only: g[b * taps + k], band b's filter; crossovers_hz n_bands - 1 values, ascending (NULL with one band) */
 arx_status arx_band_filters(int32_t sample_rate, const double* crossovers_hz, int32_t n_bands, int32_t taps,
@@ -879,6 +880,95 @@ arx_status arx_combine_bands(arx_renderer* r,
                              double* ms);                                 /* device time of the call, or NULL */
 /* host only: scratch bytes of a call by the formula above; 0 for arguments the call rejects */
 uint64_t arx_debug_combine_bytes(size_t ir_len, int32_t n_bands, int32_t taps);
+
+/* Band IRs for a batch of listeners in one call, from one recorded path set.
+ *
+ * arx_render_listeners answers many listeners for the scene's one absorption; arx_render_bands answers every
+ * band for the renderer's one listener.  arx_render_listener_bands joins them: entry (j, b) of its outputs
+ * is, bit for bit, what this loop gives,
+ *
+ *   saved = listener
+ *   for j in 0..n-1: arx_set_listener(poses[j]); arx_render_bands(...); [arx_combine_bands(set j, filters)]
+ *   arx_set_listener(saved)
+ *
+ * -- both IR channels, the three counters, the three arx_acoustics and the broadband pair -- and so, by
+ * arx_render_bands' contract, the frame of a renderer at pose j whose scene carries table[b].  ir_left /
+ * ir_right are [listener][band][ir_len] (n x n_bands x ir_len floats each, n_bands = arx_band_count; host or
+ * device memory; both NULL: no band IRs); with `filters` (arx_band_filters' n_bands x taps doubles, host or
+ * device memory) bb_left / bb_right take one broadband pair per listener, [listener][ir_len] --
+ * arx_convolute_walk's layout -- each arx_combine_bands of that listener's bands; acoustics n x n_bands x 3
+ * and results n x n_bands are host memory (NULL: none); *ms the device time of the whole call, its warm
+ * launches included (recorded only when ms is given).  n == 0: ARX_OK, nothing is touched.
+ *
+ * How.  The batched route is arx_render_listeners' -- chunks of receiver slots, one refit, one filter pass
+ * over the stored segments for eight listeners at a time, the listeners' work items -- with a band chain as
+ * the candidate kernel.  A candidate query's energy per band needs the chain of the ray's earlier hits:
+ * those are the recorded triangle ids, one 16-B record load and one table row each, with no geometry (the
+ * position, distance and direction before every query are in the filter's planes), so a candidate ray is
+ * walked once from bounce 0 and only its candidate bounces run the receiver query.  A band's query count
+ * needs every ray: base_b(ray), the queries band b makes along the ray's scene-only recording, does not
+ * depend on the listener and is counted once per call for all rays (8 B per ray); a ray that a listener's
+ * receiver ends at query k took exactly max(0, base_b(ray) - (k + 1)) queries of band b away, and only
+ * candidate rays can be ended, so per listener and band queries = sum over all rays of base_b - sum over
+ * the ended rays of max(0, base_b - (k + 1)).  A flagged last query (a miss, or a scene triangle marked as
+ * receiver) is always a candidate and always the ray's last recorded query: it cuts nothing.  Per chunk
+ * then, per (listener, band), a finalize and, when asked, an analysis; with filters one band synthesis per
+ * listener; the copies.  The batched route synchronises once, at the call's end.
+ *
+ * Routing.  No recording of the current key yet: warm launches as in arx_render_bands, at poses[0],
+ * counted in warm_launches.  Cache off, launch not cacheable or records over the cap: ARX_ERR_NOT_READY, as
+ * in arx_render_bands; also without a scene or without a table.  A recording without filter state (filter
+ * off, no room for its planes, max_bounces > 64), a receiver too large for the device refit, or no room
+ * for the scratch: every pose takes the one-listener route -- arx_set_listener + arx_render_bands
+ * (+ arx_combine_bands) inside the call, each ending synchronised -- and reports ARX_LISTENER_SINGLE.  A
+ * single pose takes it in place when the emitter lies inside its grown receiver box or its receiver cannot
+ * be put on the quantization grid.  Before the first chunk the grid is grown once to hold every pose's
+ * receiver.  A slot refit that leaves the grid ends the call with ARX_ERR_INTERNAL.
+ *
+ * ARX_ERR_INVALID_ARGUMENT: arx_render_listeners' cases (NULL r, NULL poses with n > 0, exactly one IR
+ * pointer NULL, a non-finite pose, more than one frame in flight, a caller's own stream, an attached
+ * histogram); exactly one of bb_left / bb_right NULL; filters without the bb pair or the pair without
+ * filters; with filters, taps even or outside [1, ARX_BAND_TAPS_MAX].
+ *
+ * What the call leaves alone: the renderer's last frame (untouched when no warm launch ran, else the last
+ * warm launch's), the records and the path filter's state; the listener is restored.  It may overwrite the
+ * scratch of arx_render_bands and of arx_combine_bands (the one-listener route).
+ *
+ * Memory, OUTSIDE arx_debug_set_path_cache's max_bytes: one scratch allocation per renderer of its own,
+ * made by the first batched call, kept across calls, freed when it must grow and at arx_destroy.
+ * arx_debug_listener_band_bytes(rays, ir_len, recv_nodes, recv_tris, n_bands, listeners) is
+ *   listeners x ( 96 x recv_nodes + 48 x recv_tris + 96 + 112    the receiver slot, its top node, the table entry
+ *               + 16 x rays + 16 x ceil(rays/1024)               the candidate list and its heads
+ *               + 16 + 64 x ceil(rays/1024)                      the candidate launch's work items
+ *               + n_bands x (16 x ir_len + 64 + 336 + 8 x ir_len)  per band: histogram, counter block, three
+ *                                                                arx_acoustics, f32 IR pair
+ *               + 64 + 8 x ir_len )                              the candidate tally's block, the broadband pair
+ *   + 8 x rays + 512                                             once per call: the per-ray band counts, the
+ *                                                                base counter block
+ * plus, not counted, one decay-curve buffer of 24 x ir_len B, the analysis kernels' scratch and the filter
+ * bank.  arx_debug_set_listener_chunk applies; the automatic chunk is the largest count, at most 64, that
+ * keeps the formula within the same 512 MiB: at 1M rays, a 2-s IR at 48 kHz, the 1 020-triangle head and 8
+ * bands, 35.4 MB per listener, so 14 listeners (481 MiB; 15 would be 514.4 MiB).  0 for negative arguments or n_bands outside
+ * [1, ARX_MAX_BANDS].
+ *
+ * Not offered here: groups, the C++ shim, app.py modes and frames in flight. */
+typedef struct arx_listener_band_result {                                                /* 48 B, no implicit padding */
+    uint64_t queries, receiver_hits, misses;   /* arx_stats' counters of this (listener, band)'s frame */
+    uint64_t candidate_rays;                   /* batched route only (the same in every band of a listener), else 0 */
+    int32_t route;                             /* ARX_LISTENER_BATCHED / ARX_LISTENER_SINGLE */
+    int32_t warm_launches;                     /* as arx_band_result's, the same in every entry */
+    uint64_t reserved2;                        /* 0 */
+} arx_listener_band_result;
+arx_status arx_render_listener_bands(arx_renderer* r, const arx_listener_pose* poses, size_t n,
+                                     float* ir_left, float* ir_right,     /* [listener][band][ir_len], or both NULL */
+                                     const double* filters, int32_t taps, /* n_bands x taps, or NULL / 0 */
+                                     float* bb_left, float* bb_right,     /* [listener][ir_len]; required iff filters */
+                                     arx_acoustics* acoustics,            /* n*n_bands*3, or NULL */
+                                     arx_listener_band_result* results,   /* n*n_bands, or NULL */
+                                     double* ms);                         /* device time of the whole call, or NULL */
+/* host only: the formula above */
+uint64_t arx_debug_listener_band_bytes(uint64_t n_rays, int32_t ir_len, int64_t recv_nodes, int64_t recv_tris,
+                                       int32_t n_bands, int32_t listeners);
 
 /* Walk-through convolution: one signal against a per-block IR schedule, in one call.
  *

@@ -1,0 +1,569 @@
+"""GPU: arx_render_listener_bands (include/arx.h) -- entry (j, b) is, bit for bit, what the loop
+arx_set_listener(poses[j]) + arx_render_bands (+ arx_combine_bands) gives, and so the frame of a renderer at
+pose j whose scene carries table[b].
+
+"Equal" means both IR channels' bits, the (queries, receiver hits, misses) counters and the bytes of the
+three arx_acoustics; every comparison is on bits.  Settings, tables and shapes are tests/test_gpu_bands.py's:
+16 kHz, 8 bounces, hrtf 0.5, base power 3.62, energy_thres = f32(e0 * 0.02); the table of a scene of T
+triangles and B bands is PCG64(7)'s uniform(0.05, 0.9, (B, T)) as f32 and the scene carries its column
+minimum; the 12-triangle box with 64 x 64 x 1 rays and emitter (-1.5, 1.2, 0), the conference stand-in with
+60 x 60 x 10 rays, the ray-pool shape (100, 100, 60) once.
+
+References, each made once per module and shared: a cache-off renderer given Scene(walls, table[b]) (box),
+the CPU oracle on world_scene with table[b] (conference), and the loop itself on a second renderer.  The
+counters below are the CPU oracle's, run on world_scene with table[b]; they pin the cases.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import pyoracle as po
+from audiorenderingv2_amd import (ArxError, AudioRenderer, RenderSettings, band_filters, octave_crossovers,
+                                  receiver_local)
+from audiorenderingv2_amd._lib import ArxAcoustics, ArxBandResult, ArxListenerBandResult, ArxListenerPose, check, lib
+from audiorenderingv2_amd.renderer import BAND_RESULT_DTYPE, LISTENER_BAND_RESULT_DTYPE
+from audiorenderingv2_amd.scene import CONFERENCE_EMITTER, Scene, _box_tris
+from conftest import oracle_threads, world_scene
+
+pytestmark = pytest.mark.gpu
+
+BOX_RAYS = (64, 64, 1)
+SMALL = (60, 60, 10)
+POOL = (100, 100, 60)
+BOX_EMITTER = (-1.5, 1.2, 0.0)
+S = dict(sample_rate=16000, base_power=3.62, max_bounces=8, hrtf_absorption_rate=0.5)
+INVALID, NOT_READY = 1, 4
+BATCHED, SINGLE = 0, 1
+
+# the last box pose holds the emitter in its grown box: the one-listener route in place
+BOX_POSES = [((1.5, 1.2, 0.3), 0.0), ((0.8, 1.6, -0.7), 120.0), ((0.4, 1.6, -0.6), 120.0), ((-1.2, 1.2, 0.2), 40.0)]
+BOX_PINNED = [  # (queries, receiver hits, misses) per band 0..4; band 4 from the five-band table
+    [(17805, 1525, 1), (16464, 1374, 0), (22653, 1939, 4), (19037, 1618, 1), (21693, 1811, 3)],
+    [(17570, 1537, 1), (15805, 1411, 0), (21852, 1962, 3), (18747, 1634, 1), (21159, 1830, 2)],
+    [(17084, 1670, 1), (15352, 1523, 0), (21151, 2070, 4), (18186, 1757, 1), (20416, 1936, 3)],
+    [(4776, 3948, 0), (4640, 3942, 0), (4984, 3968, 0), (4920, 3963, 0), (4933, 3962, 0)],
+]
+# home; two with overlapping boxes; near the emitter; outside the room and off the first grid
+CONF_POSES = [((5.0, 1.2, 2.0), 0.0), ((4.0, 1.2, 1.0), 15.0), ((4.4, 1.2, 1.2), 100.0), ((-7.5, 1.2, 0.0), 80.0),
+              ((14.0, 1.2, 0.0), 0.0)]
+CONF_PINNED = [
+    [(194952, 87, 7), (178543, 72, 2), (235970, 152, 6), (183296, 70, 6)],
+    [(194974, 59, 7), (178573, 53, 2), (236069, 99, 6), (183320, 53, 6)],
+    [(194968, 71, 7), (178569, 57, 2), (236034, 125, 6), (183310, 59, 6)],
+    [(189299, 2089, 6), (173539, 1922, 2), (228990, 2300, 5), (178141, 1981, 5)],
+    [(195037, 0, 7), (178639, 0, 2), (236214, 0, 6), (183352, 0, 6)],
+]
+# nine poses for the chunking case: a ragged second chunk and a ragged eight-wide filter pass at chunk 8
+NINE = CONF_POSES + [((1.0, 1.2, -0.5), 30.0), ((8.5, 2.5, -4.5), 200.0), ((-2.0, 1.6, 3.0), 310.0), CONF_POSES[0]]
+
+
+def n_of(rays):
+    return rays[0] * rays[1] * rays[2]
+
+
+def thres(rays, factor=0.02):
+    e0 = np.float32(3.62 / (n_of(rays) * 4.18879020478))
+    return float(np.float32(e0 * np.float32(factor)))
+
+
+def arr(poses):
+    return np.array([[*p, yaw] for p, yaw in poses], np.float32)
+
+
+def band_table(n_bands, n_tris):
+    return np.random.Generator(np.random.PCG64(7)).uniform(0.05, 0.9, (n_bands, n_tris)).astype(np.float32)
+
+
+def box_scene(marked, n_bands):
+    """(scene with the column-minimum absorption, table)."""
+    walls = _box_tris(np.array([[-3.0, 0.0, -2.0]], np.float32), np.array([[3.0, 3.0, 2.0]], np.float32))
+    names = ["wall"] * 12
+    tris = walls
+    if marked:
+        marks = np.array([[-2.5, 0.4, -1.0, -2.5, 0.4, 1.0, -2.5, 2.4, 0.0],
+                          [-0.5, 2.6, -1.0, -0.5, 2.6, 1.0, -2.5, 2.6, 0.0]], np.float32)
+        tris = np.concatenate([walls, marks])
+        names = names + ["receiver_left", "receiver_right"]
+    table = band_table(n_bands, len(tris))
+    if marked:
+        table[:, 12], table[:, 13] = -1.0, -2.0
+    return Scene(tris, table.min(axis=0), names), table
+
+
+def conf_scene(conference, n_bands=4):
+    table = band_table(n_bands, conference.n_tris)
+    return Scene(conference.tri_v, table.min(axis=0), conference.names), table
+
+
+def make(scene, rays, cache, emitter, listener, table=None, **over):
+    kw = {**S, "rays": rays, "energy_thres": thres(rays), **over}
+    r = AudioRenderer(RenderSettings(**kw), scene=scene, receiver=receiver_local())
+    r.set_path_cache(1 if cache else 0)
+    r.setEmitterPosInOptix(emitter)
+    r.setSphereCenterInOptix(*listener)
+    if table is not None:
+        r.set_band_absorption(table)
+    return r
+
+
+EACH = 3 * C.sizeof(ArxAcoustics)
+
+
+def call(r, poses, filters=None, irs=True, acoustics=True):
+    """arx_render_listener_bands with every output: cells[j][b] = (L bits, R bits, counters, acoustics bytes),
+    the [K, B] stats array and the broadband pair's bits."""
+    P = arr(poses)
+    k, B, n = len(poses), r.n_bands, r.ir_length
+    L, R = np.zeros((k, B, n), np.float32), np.zeros((k, B, n), np.float32)
+    bl, br = np.zeros((k, n), np.float32), np.zeros((k, n), np.float32)
+    ac = (ArxAcoustics * (3 * k * B))()
+    res = (ArxListenerBandResult * (k * B))()
+    ms = C.c_double(-1.0)
+    g = None if filters is None else np.ascontiguousarray(filters, np.float64)
+    check(lib().arx_render_listener_bands(
+        r.handle, P.ctypes.data_as(C.POINTER(ArxListenerPose)), k, L.ctypes.data if irs else None,
+        R.ctypes.data if irs else None, None if g is None else g.ctypes.data, 0 if g is None else g.shape[1],
+        None if g is None else bl.ctypes.data, None if g is None else br.ctypes.data, ac if acoustics else None, res,
+        C.byref(ms)))
+    assert ms.value > 0.0
+    stats = np.frombuffer(res, dtype=LISTENER_BAND_RESULT_DTYPE, count=k * B).copy().reshape(k, B)
+    assert not stats["reserved2"].any()
+    assert len(set(stats["warm_launches"].reshape(-1).tolist())) == 1
+    raw = bytes(ac)
+    cells = [[(L[j, b].view(np.uint32), R[j, b].view(np.uint32),
+               (int(stats[j, b]["queries"]), int(stats[j, b]["receiver_hits"]), int(stats[j, b]["misses"])),
+               raw[(j * B + b) * EACH:(j * B + b + 1) * EACH] if acoustics else None) for b in range(B)] for j in range(k)]
+    bb = None if g is None else (bl.view(np.uint32), br.view(np.uint32))
+    return {"cells": cells, "stats": stats, "bb": bb}
+
+
+def render_bands(r):
+    """arx_render_bands at the renderer's listener: per band the same tuple, and the IR arrays."""
+    B, n = r.n_bands, r.ir_length
+    L, R = np.zeros((B, n), np.float32), np.zeros((B, n), np.float32)
+    ac = (ArxAcoustics * (3 * 8))()
+    res = (ArxBandResult * 8)()
+    check(lib().arx_render_bands(r.handle, L.ctypes.data, R.ctypes.data, ac, res, None))
+    stats = np.frombuffer(res, dtype=BAND_RESULT_DTYPE, count=8).copy()
+    raw = bytes(ac)
+    return [(L[b].view(np.uint32), R[b].view(np.uint32),
+             (int(stats[b]["queries"]), int(stats[b]["receiver_hits"]), int(stats[b]["misses"])),
+             raw[b * EACH:(b + 1) * EACH]) for b in range(B)], (L, R)
+
+
+def loop(r, poses, filters=None):
+    """The loop the call stands for, on r: cells[j][b], and per pose arx_combine_bands' pair."""
+    cells, bb = [], []
+    for p in poses:
+        r.setSphereCenterInOptix(*p)
+        bands, (L, R) = render_bands(r)
+        cells.append(bands)
+        if filters is not None:
+            out = r.combine_bands((L, R), filters)["ir"]
+            bb.append((out[0].view(np.uint32), out[1].view(np.uint32)))
+    return cells, bb
+
+
+def same(got, want, what, acoustics=True):
+    assert got[2] == want[2], (what, got[2], want[2])
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), what
+    if acoustics and want[3] is not None:  # the oracle has no analysis
+        assert got[3] == want[3], what
+
+
+def same_cells(got, want, what, acoustics=True):
+    assert len(got) == len(want)
+    for j, (gj, wj) in enumerate(zip(got, want)):
+        assert len(gj) == len(wj)
+        for b, (g, w) in enumerate(zip(gj, wj)):
+            same(g, w, f"{what}: pose {j} band {b}", acoustics)
+
+
+def counters(cells):
+    return [[c[2] for c in row] for row in cells]
+
+
+def routes(out):
+    return [int(x) for x in out["stats"]["route"][:, 0]]
+
+
+class BoxRefs:
+    """Cache-off renderers given Scene(walls, table[b]), one per (table width, band): their frames by pose."""
+
+    def __init__(self):
+        self.rs, self.frames = {}, {}
+
+    def want(self, n_bands, band, pose):
+        if (n_bands, band) not in self.rs:
+            scene, table = box_scene(False, n_bands)
+            self.rs[(n_bands, band)] = make(Scene(scene.tri_v, table[band], scene.names), BOX_RAYS, False, BOX_EMITTER, pose)
+        key = (n_bands, band, pose)
+        if key not in self.frames:
+            r = self.rs[(n_bands, band)]
+            r.setSphereCenterInOptix(*pose)
+            r.render()
+            r.analyze_ir()
+            L, R = r.get_ir()
+            st = r.stats()
+            out = (ArxAcoustics * 3)()
+            for ch in range(3):
+                assert lib().arx_get_acoustics(r.handle, ch, C.byref(out[ch])) == 0
+            self.frames[key] = (L.view(np.uint32).copy(), R.view(np.uint32).copy(),
+                                (st["queries"], st["receiver_hits"], st["misses"]), bytes(out))
+        return self.frames[key]
+
+    def close(self):
+        for r in self.rs.values():
+            r.close()
+
+
+@pytest.fixture(scope="module")
+def box_refs():
+    x = BoxRefs()
+    yield x
+    x.close()
+
+
+class Loops:
+    """Second renderers that run the loop, one per (scene tag, settings), and their cells by pose."""
+
+    def __init__(self):
+        self.rs, self.cells = {}, {}
+
+    def want(self, tag, build, poses):
+        if tag not in self.rs:
+            self.rs[tag] = build()
+        out = []
+        for p in poses:
+            if (tag, p) not in self.cells:
+                self.cells[(tag, p)] = loop(self.rs[tag], [p])[0][0]
+            out.append(self.cells[(tag, p)])
+        return out
+
+    def close(self):
+        for r in self.rs.values():
+            r.close()
+
+
+@pytest.fixture(scope="module")
+def loops():
+    x = Loops()
+    yield x
+    x.close()
+
+
+def box_renderer(n_bands=4, marked=False, rays=BOX_RAYS, **over):
+    scene, table = box_scene(marked, n_bands)
+    return make(scene, rays, True, BOX_EMITTER, BOX_POSES[0], table, **over)
+
+
+@pytest.fixture(scope="module")
+def conf_auto(conference):
+    """The nine conference poses in one call at the automatic chunk, every output."""
+    scene, table = conf_scene(conference)
+    r = make(scene, SMALL, True, CONFERENCE_EMITTER, CONF_POSES[0], table)
+    try:
+        return call(r, NINE)
+    finally:
+        r.close()
+
+
+def oracle_frame(scene, absorption, rays, emitter, listener):
+    s = RenderSettings(**{**S, "rays": rays, "energy_thres": thres(rays)})
+    tv, ta = world_scene(Scene(scene.tri_v, absorption, scene.names), listener[0], listener[1])
+    osc = po.Scene(tv, ta, bvh=True)
+    p = po.make_params(rays=s.rays, sample_rate=s.sample_rate, ir_seconds=s.ir_length_in_seconds, base_power=s.base_power,
+                       energy_thres=s.energy_thres, max_bounces=s.max_bounces, hrtf=s.hrtf_absorption_rate, mono=s.mono,
+                       seed=s.seed, emitter=emitter, listener=listener[0])
+    L, R, st = osc.trace(p, threads=oracle_threads())
+    irl, irr = po.finalize_ir(p, L, R)
+    return irl.view(np.uint32), irr.view(np.uint32), (st["queries"], st["receiver_hits"], st["misses"]), None
+
+
+def test_box_four_bands_four_poses_equal_their_own_renderers(box_refs):
+    """1. Each (pose, band) against a cache-off renderer given Scene(walls, table[b]) at that pose."""
+    r = box_renderer()
+    try:
+        out = call(r, BOX_POSES)
+        for j, p in enumerate(BOX_POSES):
+            for b in range(4):
+                same(out["cells"][j][b], box_refs.want(4, b, p), f"pose {j} band {b}")
+        assert counters(out["cells"]) == [row[:4] for row in BOX_PINNED]
+        assert routes(out) == [BATCHED, BATCHED, BATCHED, SINGLE]
+        cand = out["stats"]["candidate_rays"]
+        for j in range(3):
+            assert 0 < int(cand[j, 0]) < n_of(BOX_RAYS) and len(set(cand[j].tolist())) == 1
+        assert not cand[3].any()
+        assert (out["stats"]["route"] == out["stats"]["route"][:, :1]).all()
+        # the Python wrapper returns the same
+        py = r.render_listener_bands(arr(BOX_POSES), irs=True, acoustics=True)
+        assert py["ir"][0].shape == (4, 4, r.ir_length) and py["stats"].shape == (4, 4) and py["ms"] > 0.0
+        assert py["broadband"] is None and len(py["acoustics"]) == 4 and len(py["acoustics"][0]) == 4
+        for j in range(4):
+            for b in range(4):
+                assert np.array_equal(py["ir"][0][j, b].view(np.uint32), out["cells"][j][b][0])
+                assert int(py["stats"][j, b]["queries"]) == out["cells"][j][b][2][0]
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("j", range(5))
+def test_conference_four_bands_five_poses_equal_the_cpu_oracle(conference, conf_auto, j):
+    """2. Each (pose, band) of the one call against the CPU oracle on world_scene with table[b]: IR bits and
+    counters (a case per pose: four oracle frames each)."""
+    scene, table = conf_scene(conference)
+    assert counters(conf_auto["cells"][:5]) == CONF_PINNED
+    assert routes(conf_auto) == [BATCHED] * 9
+    for b in range(4):
+        same(conf_auto["cells"][j][b], oracle_frame(scene, table[b], SMALL, CONFERENCE_EMITTER, CONF_POSES[j]),
+             f"pose {j} band {b}")
+
+
+def conf_loop_renderer(conference):
+    scene, table = conf_scene(conference)
+    return make(scene, SMALL, True, CONFERENCE_EMITTER, CONF_POSES[0], table)
+
+
+def test_the_call_is_the_loop(conference, conf_auto, loops):
+    """3. The same poses against arx_set_listener + arx_render_bands on a second renderer, acoustics included."""
+    want = loops.want("conf", lambda: conf_loop_renderer(conference), NINE)
+    same_cells(conf_auto["cells"], want, "conference")
+    assert all(c[3] is not None and any(c[3]) for row in conf_auto["cells"] for c in row)
+
+
+@pytest.mark.parametrize("n_bands", [1, 3, 5, 8])
+def test_both_widths_and_their_padding(loops, n_bands):
+    """4. B = 1, 3 (width 4, padded) and 5, 8 (width 8, padded and full), two poses, against the loop."""
+    r = box_renderer(n_bands)
+    try:
+        out = call(r, BOX_POSES[:2])
+        assert routes(out) == [BATCHED, BATCHED]
+        same_cells(out["cells"], loops.want(f"box{n_bands}", lambda: box_renderer(n_bands), BOX_POSES[:2]), f"B = {n_bands}")
+        if n_bands == 5:
+            assert counters(out["cells"]) == BOX_PINNED[:2]
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("chunk", [1, 3, 8])
+def test_chunking_gives_the_same_bits(conference, conf_auto, chunk):
+    """5. Forced chunks of 1, of 3 (3, 3, 3) and of 8 (8 + 1: a ragged second chunk and a filter pass of one
+    listener) against the automatic chunk's bits."""
+    scene, table = conf_scene(conference)
+    r = make(scene, SMALL, True, CONFERENCE_EMITTER, CONF_POSES[0], table)
+    try:
+        r.set_listener_chunk(chunk)
+        out = call(r, NINE)
+        assert routes(out) == [BATCHED] * 9
+        same_cells(out["cells"], conf_auto["cells"], f"chunk {chunk}")
+        assert np.array_equal(out["stats"]["candidate_rays"], conf_auto["stats"]["candidate_rays"])
+    finally:
+        r.close()
+
+
+SETTINGS = [("no-threshold", False, dict(energy_thres=0.0)), ("threshold", False, dict(energy_thres=thres(BOX_RAYS, 0.2))),
+            ("mono", False, dict(mono=True)), ("hrtf-0.25", False, dict(hrtf_absorption_rate=0.25)), ("marked", True, {})]
+
+
+@pytest.mark.parametrize("what,marked,over", SETTINGS, ids=[s[0] for s in SETTINGS])
+def test_settings(loops, what, marked, over):
+    """6. energy_thres 0 (no band dies), a threshold at which bands die before the recording does, mono,
+    hrtf 0.25, and the box with its own receiver-marked triangles: two poses against the loop."""
+    r = box_renderer(4, marked, **over)
+    try:
+        out = call(r, BOX_POSES[:2])
+        assert routes(out) == [BATCHED, BATCHED]
+        same_cells(out["cells"], loops.want(f"settings-{what}", lambda: box_renderer(4, marked, **over), BOX_POSES[:2]), what)
+        q = [[c[2][0] for c in row] for row in out["cells"]]
+        if what == "no-threshold":
+            # a band's queries differ from another's only through when its energy dies: none does
+            assert all(len(set(row)) == 1 for row in q)
+        if what == "threshold":
+            # the recording runs at least the longest band's queries, and a shorter band died before it
+            assert all(min(row) < max(row) for row in q)
+        if what == "mono":
+            assert all(np.array_equal(c[0], c[1]) for row in out["cells"] for c in row)
+        if what == "marked":
+            plain = loops.want("box4", lambda: box_renderer(4), BOX_POSES[:2])
+            assert counters(out["cells"]) != counters(plain)  # the marks do end rays
+    finally:
+        r.close()
+
+
+def status_of(fn):
+    try:
+        fn()
+    except ArxError as e:
+        return e.status, str(e)
+    return 0, ""
+
+
+def test_routing(box_refs, loops):
+    """7. A cold start warms the cache itself; without filter state, and with 65 bounces, every pose takes the
+    one-listener route with equal bits; cache off and no table are ARX_ERR_NOT_READY."""
+    r = box_renderer()
+    try:
+        out = call(r, BOX_POSES[:2])  # cold
+        warm = out["stats"]["warm_launches"]
+        assert 1 <= int(warm[0, 0]) <= 3 and (warm == warm[0, 0]).all()
+        assert routes(out) == [BATCHED, BATCHED]
+        for j in range(2):
+            for b in range(4):
+                same(out["cells"][j][b], box_refs.want(4, b, BOX_POSES[j]), f"cold pose {j} band {b}")
+        r.set_path_cache(0)
+        st, msg = status_of(lambda: call(r, BOX_POSES[:2]))
+        assert st == NOT_READY and "off" in msg, msg
+        r.set_path_cache(1)
+        r.set_band_absorption(None)
+        st, msg = status_of(lambda: call(r, BOX_POSES[:2]))
+        assert st == NOT_READY and "arx_set_band_absorption" in msg, msg
+    finally:
+        r.close()
+    r = box_renderer()
+    try:
+        r.set_path_filter(False)  # before the first launch: the records come without filter state
+        out = call(r, BOX_POSES[:2])
+        assert routes(out) == [SINGLE, SINGLE] and not out["stats"]["candidate_rays"].any()
+        assert 1 <= int(out["stats"]["warm_launches"][0, 0]) <= 3
+        for j in range(2):
+            for b in range(4):
+                same(out["cells"][j][b], box_refs.want(4, b, BOX_POSES[j]), f"filter off pose {j} band {b}")
+    finally:
+        r.close()
+    deep = dict(rays=(16, 16, 16), max_bounces=65, energy_thres=thres((16, 16, 16)))
+    r = box_renderer(4, False, **deep)
+    try:
+        out = call(r, BOX_POSES[:2])
+        assert routes(out) == [SINGLE, SINGLE]
+        same_cells(out["cells"], loops.want("deep", lambda: box_renderer(4, False, **deep), BOX_POSES[:2]), "65 bounces")
+    finally:
+        r.close()
+
+
+def test_broadband(loops):
+    """8. bb of pose j is arx_combine_bands on set j; auralise_walk_bands is the call followed by convolute_walk."""
+    g = band_filters(16000, octave_crossovers([250.0, 1000.0, 4000.0, 8000.0])[:3], 255)
+    assert g.shape == (4, 255)
+    r = box_renderer()
+    r2 = box_renderer()
+    try:
+        out = call(r, BOX_POSES, filters=g)
+        want_cells, want_bb = loop(r2, BOX_POSES, g)
+        same_cells(out["cells"], want_cells, "with filters")
+        assert routes(out) == [BATCHED, BATCHED, BATCHED, SINGLE]
+        for j in range(4):
+            assert np.array_equal(out["bb"][0][j], want_bb[j][0]) and np.array_equal(out["bb"][1][j], want_bb[j][1]), j
+            assert out["bb"][0][j].any()
+        # the broadband set alone: no band IRs, no analysis
+        only = call(r, BOX_POSES, filters=g, irs=False, acoustics=False)
+        assert np.array_equal(only["bb"][0], out["bb"][0]) and np.array_equal(only["bb"][1], out["bb"][1])
+        # the walk: the same frames as the two steps by hand
+        x = np.random.Generator(np.random.PCG64(11)).standard_normal(3 * 4096)
+        walk = r.auralise_walk_bands(arr(BOX_POSES), x, g, block_frames=4096)
+        py = r.render_listener_bands(arr(BOX_POSES), acoustics=False, filters=g)
+        assert np.array_equal(py["broadband"][0].view(np.uint32), out["bb"][0])
+        by_hand = r.convolute_walk(py["broadband"], walk["ir_of_block"], x, 4096, 4096)
+        assert np.array_equal(walk["out"].view(np.uint64), by_hand["out"].view(np.uint64)) and walk["out"].any()
+    finally:
+        r.close()
+        r2.close()
+
+
+def test_state_after_the_call(loops):
+    """9. The listener restored, the last frame untouched, the two calls it joins unharmed, no stale base counts."""
+    r = box_renderer()
+    try:
+        for _ in range(3):
+            r.render()
+        r.analyze_ir()
+        before = (r.get_ir()[0].view(np.uint32).copy(), r.get_ir()[1].view(np.uint32).copy(), r.stats())
+        out = call(r, BOX_POSES[1:3])
+        assert not out["stats"]["warm_launches"].any()
+        after = (r.get_ir()[0].view(np.uint32), r.get_ir()[1].view(np.uint32), r.stats())
+        assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])
+        assert [before[2][k] for k in ("queries", "receiver_hits", "misses")] == \
+               [after[2][k] for k in ("queries", "receiver_hits", "misses")]
+        # the listener is the one set before: arx_render_bands answers for it
+        want = loops.want("box4", lambda: box_renderer(4), BOX_POSES[:3])
+        bands, _ = render_bands(r)
+        same_cells([bands], want[:1], "arx_render_bands after the call")
+        # arx_render_listeners after the call is the loop of arx_render
+        rl = r.render_listeners(arr(BOX_POSES[:2]), irs=True)
+        for j, p in enumerate(BOX_POSES[:2]):
+            r.setSphereCenterInOptix(*p)
+            r.render()
+            L, R = r.get_ir()
+            assert np.array_equal(rl["ir"][0][j].view(np.uint32), L.view(np.uint32)), j
+            assert np.array_equal(rl["ir"][1][j].view(np.uint32), R.view(np.uint32)), j
+            assert int(rl["stats"][j]["queries"]) == r.stats()["queries"]
+        # and the call after them still gives its own bits
+        same_cells(call(r, BOX_POSES[:3])["cells"], want, "second call")
+        # another table: the base counts follow it
+        scene, table = box_scene(False, 4)
+        other = np.ascontiguousarray(table[::-1])
+        r.set_band_absorption(other)
+        out = call(r, BOX_POSES[:3])
+        same_cells(out["cells"], [row[::-1] for row in want], "the table reversed")
+    finally:
+        r.close()
+
+
+def test_ray_pool_shape_against_the_loop(conference):
+    """10. 600 000 rays, once: the records index the cache's own copy of the sorted direction buffer."""
+    scene, table = conf_scene(conference)
+    r = make(scene, POOL, True, CONFERENCE_EMITTER, CONF_POSES[0], table)
+    r2 = make(scene, POOL, True, CONFERENCE_EMITTER, CONF_POSES[0], table)
+    try:
+        out = call(r, CONF_POSES[:2])
+        assert routes(out) == [BATCHED, BATCHED]
+        assert 1 <= int(out["stats"]["warm_launches"][0, 0]) <= 3
+        same_cells(out["cells"], loop(r2, CONF_POSES[:2])[0], "pool")
+    finally:
+        r.close()
+        r2.close()
+
+
+def test_arguments():
+    """11. Every ARX_ERR_INVALID_ARGUMENT; n == 0 is ARX_OK and touches nothing."""
+    r = box_renderer()
+    try:
+        f = lib().arx_render_listener_bands
+        n = r.ir_length
+        P = arr(BOX_POSES[:2])
+        pp = P.ctypes.data_as(C.POINTER(ArxListenerPose))
+        buf = [np.full((2, 4, n), 7.0, np.float32) for _ in range(2)]
+        bb = [np.full((2, n), 7.0, np.float32) for _ in range(2)]
+        g = band_filters(16000, [500.0, 1000.0, 2000.0], 31)
+        gp = g.ctypes.data
+        res = (ArxListenerBandResult * 8)()
+        assert f(None, pp, 2, None, None, None, 0, None, None, None, None, None) == INVALID
+        assert f(None, None, 0, None, None, None, 0, None, None, None, None, None) == INVALID
+        assert f(r.handle, None, 2, None, None, None, 0, None, None, None, None, None) == INVALID
+        assert f(r.handle, pp, 2, buf[0].ctypes.data, None, None, 0, None, None, None, None, None) == INVALID
+        assert f(r.handle, pp, 2, None, buf[1].ctypes.data, None, 0, None, None, None, None, None) == INVALID
+        assert f(r.handle, pp, 2, None, None, gp, 31, bb[0].ctypes.data, None, None, None, None) == INVALID
+        assert f(r.handle, pp, 2, None, None, gp, 31, None, bb[1].ctypes.data, None, None, None) == INVALID
+        assert f(r.handle, pp, 2, None, None, gp, 31, None, None, None, None, None) == INVALID
+        assert f(r.handle, pp, 2, None, None, None, 0, bb[0].ctypes.data, bb[1].ctypes.data, None, None, None) == INVALID
+        for taps in (0, 30, -1, 8193):
+            assert f(r.handle, pp, 2, None, None, gp, taps, bb[0].ctypes.data, bb[1].ctypes.data, None, None, None) == INVALID
+        bad = P.copy()
+        bad[1, 2] = np.nan
+        assert f(r.handle, bad.ctypes.data_as(C.POINTER(ArxListenerPose)), 2, None, None, None, 0, None, None, None, res,
+                 None) == INVALID
+        r.set_frames_in_flight(2)
+        assert f(r.handle, pp, 2, None, None, None, 0, None, None, None, res, None) == INVALID
+        r.set_frames_in_flight(1)
+        # n == 0: nothing is written, nothing is launched, no table or cache is needed
+        state = r.path_cache_state()["state"]
+        assert f(r.handle, None, 0, buf[0].ctypes.data, buf[1].ctypes.data, gp, 31, bb[0].ctypes.data, bb[1].ctypes.data,
+                 None, res, None) == 0
+        assert all((b == 7.0).all() for b in buf + bb) and not bytes(res).strip(b"\0")
+        assert r.path_cache_state()["state"] == state
+        assert status_of(lambda: r.render_listener_bands(np.zeros((0, 4), np.float32)))[0] == 0
+        # nothing above left the renderer unusable
+        out = call(r, BOX_POSES[:2])
+        assert counters(out["cells"]) == [row[:4] for row in BOX_PINNED[:2]]
+    finally:
+        r.close()
