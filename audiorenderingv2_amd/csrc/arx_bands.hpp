@@ -9,12 +9,10 @@
 
 #include <cstdint>
 
+#include "arx_batch_plan.hpp"  // kMaxBands, kBandCounterWords
 #include "arx_layout.hpp"
 
 namespace arx {
-
-constexpr int32_t kMaxBands = 8;         // ARX_MAX_BANDS
-constexpr int32_t kBandCounterWords = 8; // a band's counter block: [0] queries [1] receiver hits [2] misses, padding
 
 // The compiled width that serves n_bands: the device table's row, so a hit fetches its bands in one or
 // two 16-B loads.

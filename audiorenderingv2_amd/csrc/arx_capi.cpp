@@ -384,11 +384,11 @@ void arx_destroy(arx_renderer* r) {
     hipFree(r->d_w4f);
     hipFree(r->d_tree_flag);
     free_path_cache(r->path_cache);
-    free_listener_batch(r->listeners);
+    free_listener_scratch(r->listeners);
     free_walk(r->walk);
     free_bands(r->bands);
     free_synth(r->synth);
-    free_listener_bands(r->listener_bands);
+    free_listener_scratch(r->listener_bands);
     if (r->h_tree_flag) hipHostFree(r->h_tree_flag);
     hipFree(r->d_conv_in);
     hipFree(r->d_conv_out);

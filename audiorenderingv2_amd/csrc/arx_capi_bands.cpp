@@ -53,19 +53,14 @@ struct SynthLayout {
 };
 SynthLayout synth_layout(size_t ir_len, int32_t n_bands, int32_t taps) {
     SynthLayout s;
-    uint64_t at = 0;
-    auto take = [&at](uint64_t bytes) {
-        const uint64_t o = at;
-        at += (bytes + 255) & ~255ull;
-        return o;
-    };
+    Take take{256};
     const uint64_t B = (uint64_t)n_bands, L = (uint64_t)ir_len;
     s.in_left = take(4 * B * L);
     s.in_right = take(4 * B * L);
     s.filters = take(8 * B * (uint64_t)taps);
     s.out_left = take(4 * L);
     s.out_right = take(4 * L);
-    s.total = at;
+    s.total = take.at;
     return s;
 }
 
@@ -73,19 +68,13 @@ SynthLayout synth_layout(size_t ir_len, int32_t n_bands, int32_t taps) {
 
 void arx::free_synth(SynthScratch& s) {
     hipFree(s.d_scratch);
-    if (s.ev0) hipEventDestroy(s.ev0);
-    if (s.ev1) hipEventDestroy(s.ev1);
+    s.timer.destroy();
     s = SynthScratch{};
 }
 
 BandScratchLayout arx::band_scratch_layout(int32_t ir_len, int32_t n_bands) {
     BandScratchLayout s;
-    uint64_t at = 0;
-    auto take = [&at](uint64_t bytes) {
-        const uint64_t o = at;
-        at += (bytes + 15) & ~15ull;
-        return o;
-    };
+    Take take{16};
     const uint64_t B = (uint64_t)n_bands, L = (uint64_t)ir_len;
     s.hist = take(B * 16 * L);
     s.counters = take(B * kBandCounterWords * 8);
@@ -93,7 +82,7 @@ BandScratchLayout arx::band_scratch_layout(int32_t ir_len, int32_t n_bands) {
     s.ir = take(B * 8 * L);  // the bands' left IRs, then their right IRs
     s.edc = take(24 * L);
     s.acou = take(acoustics_scratch_bytes());
-    s.total = at;
+    s.total = take.at;
     return s;
 }
 
@@ -101,9 +90,37 @@ void arx::free_bands(BandState& b) {
     hipFree(b.d_table);
     hipFree(b.d_scratch);
     if (b.h_pinned) hipHostFree(b.h_pinned);
-    if (b.ev0) hipEventDestroy(b.ev0);
-    if (b.ev1) hipEventDestroy(b.ev1);
+    b.timer.destroy();
     b = BandState{};
+}
+
+arx_status arx::record_for_bands(arx_renderer* r, uint64_t N, const arx_listener_pose* pose, ReplayProbe* probe, int32_t* warm) {
+    arx_status st;
+    for (;;) {
+        if ((st = trace_rays(r, 0, N, false, false, probe)) != ARX_OK) return st;
+        if (probe->recorded) return ARX_OK;
+        const int32_t would = probe->state;  // what the next launch would do
+        if (would == kPathOff) return fail(ARX_ERR_NOT_READY, "a band render replays the path cache, which is off");
+        if (would == kPathNotCacheable)
+            return fail(ARX_ERR_NOT_READY, "this launch is not cacheable (global stack, CW4 or f32 nodes): no records to replay");
+        if (would == kPathOverCap)
+            return fail(ARX_ERR_NOT_READY,
+                        "the launch's records (%llu B) are over the path cache's cap or do not fit on the device "
+                        "(arx_debug_set_path_cache max_bytes)",
+                        (unsigned long long)arx_debug_path_cache_bytes(N, r->cfg.max_bounces));
+        if (*warm == 3) return fail(ARX_ERR_NOT_READY, "the path cache did not record within three launches");
+        if (*warm == 0 && pose && (st = arx_set_listener(r, pose->x, pose->y, pose->z, pose->yaw_deg)) != ARX_OK) return st;
+        if ((st = arx_render(r, nullptr)) != ARX_OK) return st;
+        ++*warm;
+    }
+}
+
+arx_status arx::finalize_and_analyse(arx_renderer* r, const unsigned long long* hist, float* irl, float* irr,
+                                     arx_acoustics* d_res, void* edc, void* acou, bool want_ir, bool analyse) {
+    const long long* h = reinterpret_cast<const long long*>(hist);
+    if (want_ir) ARX_HIP(launch_finalize_ir(h, irl, irr, r->ir_len, ir_unit(r->cfg), r->cfg.is_mono, r->stream));
+    if (analyse) ARX_HIP(launch_acoustics(acoustics_args(r, h, static_cast<long long*>(edc), d_res, acou), r->stream));
+    return ARX_OK;
 }
 
 extern "C" {
@@ -191,31 +208,12 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     const int32_t B = bs.n_bands;
     const size_t ir_len = (size_t)r->ir_len;
     const bool timed = ms != nullptr;  // around the whole call, its warm launches included
-    if (timed) {
-        if (!bs.ev0) ARX_HIP(hipEventCreate(&bs.ev0));
-        if (!bs.ev1) ARX_HIP(hipEventCreate(&bs.ev1));
-        ARX_HIP(hipEventRecord(bs.ev0, r->stream));
-    }
+    arx_status st;
+    if (timed && (st = bs.timer.begin(r->stream)) != ARX_OK) return st;
     // 1. the recording: ordinary launches of the current settings until the cache holds the key's records
     ReplayProbe probe;
     int32_t warm = 0;
-    arx_status st;
-    for (;;) {
-        if ((st = trace_rays(r, 0, N, false, false, &probe)) != ARX_OK) return st;
-        if (probe.recorded) break;
-        const int32_t would = probe.state;  // what the next launch would do
-        if (would == kPathOff) return fail(ARX_ERR_NOT_READY, "a band render replays the path cache, which is off");
-        if (would == kPathNotCacheable)
-            return fail(ARX_ERR_NOT_READY, "this launch is not cacheable (global stack, CW4 or f32 nodes): no records to replay");
-        if (would == kPathOverCap)
-            return fail(ARX_ERR_NOT_READY,
-                        "the launch's records (%llu B) are over the path cache's cap or do not fit on the device "
-                        "(arx_debug_set_path_cache max_bytes)",
-                        (unsigned long long)arx_debug_path_cache_bytes(N, r->cfg.max_bounces));
-        if (warm == 3) return fail(ARX_ERR_NOT_READY, "the path cache did not record within three launches");
-        if ((st = arx_render(r, nullptr)) != ARX_OK) return st;
-        ++warm;
-    }
+    if ((st = record_for_bands(r, N, nullptr, &probe, &warm)) != ARX_OK) return st;
     // 2. the scratch and the pinned block of the host-side outputs
     if (!bs.h_pinned)
         ARX_HIP(hipHostMalloc(&bs.h_pinned, kMaxBands * (kBandCounterWords * 8 + 3 * sizeof(arx_acoustics)),
@@ -239,17 +237,10 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     ba.n_tris = bs.n_tris;
     ba.n_bands = B;
     ARX_HIP(launch_band_replay(probe.args, ba, r->stream));
-    const double unit = ir_unit(r->cfg);
-    for (int32_t b = 0; b < B; ++b) {
-        const long long* h = reinterpret_cast<const long long*>(d_hist + (size_t)b * 2 * ir_len);
-        if (ir_left)
-            ARX_HIP(launch_finalize_ir(h, d_irl + (size_t)b * ir_len, d_irr + (size_t)b * ir_len, r->ir_len, unit,
-                                       r->cfg.is_mono, r->stream));
-        if (acoustics)
-            ARX_HIP(launch_acoustics(acoustics_args(r, h, reinterpret_cast<long long*>(base + sc.edc), d_res + 3 * b,
-                                                    base + sc.acou),
-                                     r->stream));
-    }
+    for (size_t b = 0; b < (size_t)B; ++b)
+        if ((st = finalize_and_analyse(r, d_hist + b * 2 * ir_len, d_irl + b * ir_len, d_irr + b * ir_len, d_res + 3 * b,
+                                       base + sc.edc, base + sc.acou, ir_left != nullptr, acoustics != nullptr)) != ARX_OK)
+            return st;
     if (ir_left) {
         ARX_HIP(hipMemcpyAsync(ir_left, d_irl, (size_t)B * ir_len * sizeof(float), hipMemcpyDefault, r->stream));
         ARX_HIP(hipMemcpyAsync(ir_right, d_irr, (size_t)B * ir_len * sizeof(float), hipMemcpyDefault, r->stream));
@@ -259,7 +250,7 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
         ARX_HIP(hipMemcpyAsync(h_res, d_res, (size_t)B * 3 * sizeof(arx_acoustics), hipMemcpyDeviceToHost, r->stream));
     // the tree as the probe's refit left it (a listener move): its off-grid flag, as arx_get_stats reads it
     ARX_HIP(hipMemcpyAsync(r->h_tree_flag, r->d_tree_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, r->stream));
-    if (timed) ARX_HIP(hipEventRecord(bs.ev1, r->stream));
+    if (timed && (st = bs.timer.end(r->stream)) != ARX_OK) return st;
     // 4. the one synchronisation, then the host-side outputs
     ARX_HIP(hipStreamSynchronize(r->stream));
     if (r->tree_gen != 0 && *r->h_tree_flag == r->tree_gen)
@@ -275,12 +266,7 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
         }
     }
     if (acoustics) std::memcpy(acoustics, h_res, (size_t)B * 3 * sizeof(arx_acoustics));
-    if (timed) {
-        float t = 0.0f;
-        ARX_HIP(hipEventElapsedTime(&t, bs.ev0, bs.ev1));
-        *ms = (double)t;
-    }
-    return ARX_OK;
+    return timed ? bs.timer.elapsed(ms) : ARX_OK;
 }
 
 int32_t arx_band_count(const arx_renderer* r) { return r ? r->bands.n_bands : 0; }
@@ -366,11 +352,8 @@ arx_status arx_combine_bands(arx_renderer* r, const float* ir_left, const float*
     }
     char* const base = static_cast<char*>(sc.d_scratch);
     const bool timed = r->timing || ms != nullptr;
-    if (timed) {
-        if (!sc.ev0) ARX_HIP(hipEventCreate(&sc.ev0));
-        if (!sc.ev1) ARX_HIP(hipEventCreate(&sc.ev1));
-        ARX_HIP(hipEventRecord(sc.ev0, r->stream));
-    }
+    if (timed)
+        if (const arx_status tb = sc.timer.begin(r->stream); tb != ARX_OK) return tb;
     BandSynthArgs a{};
     a.ir_left = reinterpret_cast<const float*>(base + lay.in_left);
     a.ir_right = reinterpret_cast<const float*>(base + lay.in_right);
@@ -388,15 +371,11 @@ arx_status arx_combine_bands(arx_renderer* r, const float* ir_left, const float*
     ARX_HIP(launch_band_synth(a, r->stream));
     ARX_HIP(hipMemcpyAsync(out_left, base + lay.out_left, out_bytes, hipMemcpyDefault, r->stream));
     ARX_HIP(hipMemcpyAsync(out_right, base + lay.out_right, out_bytes, hipMemcpyDefault, r->stream));
-    if (timed) ARX_HIP(hipEventRecord(sc.ev1, r->stream));
+    if (timed)
+        if (const arx_status te = sc.timer.end(r->stream); te != ARX_OK) return te;
     if (const arx_status d = fif_done_conv(r); d != ARX_OK) return d;
     ARX_HIP(hipStreamSynchronize(r->stream));
-    if (ms) {
-        float el = 0.0f;
-        ARX_HIP(hipEventElapsedTime(&el, sc.ev0, sc.ev1));
-        *ms = (double)el;
-    }
-    return ARX_OK;
+    return ms ? sc.timer.elapsed(ms) : ARX_OK;
 }
 
 uint64_t arx_debug_combine_bytes(size_t ir_len, int32_t n_bands, int32_t taps) {

@@ -504,11 +504,8 @@ arx_status arx_convolute_walk(arx_renderer* r, const float* ir_left, const float
     }
     char* base = static_cast<char*>(w.d_scratch);
     const bool timed = r->timing || ms != nullptr;
-    if (timed) {
-        if (!w.ev0) ARX_HIP(hipEventCreate(&w.ev0));
-        if (!w.ev1) ARX_HIP(hipEventCreate(&w.ev1));
-        ARX_HIP(hipEventRecord(w.ev0, r->stream));
-    }
+    if (timed)
+        if (const arx_status tb = w.timer.begin(r->stream); tb != ARX_OK) return tb;
     if (w.tw_n != lay.N) {
         if (w.h_tw.size() != 2 * (size_t)lay.N) walk_twiddle_table(lay.N, w.h_tw);
         w.tw_n = 0;
@@ -544,14 +541,12 @@ arx_status arx_convolute_walk(arx_renderer* r, const float* ir_left, const float
     a.tile = w.forced_tile > 0 ? w.forced_tile : kWalkTile;
     ARX_HIP(launch_walk(a, r->stream));
     ARX_HIP(hipMemcpyAsync(out, base + lay.out, 2 * n_blocks * (size_t)B * sizeof(double), hipMemcpyDefault, r->stream));
-    if (timed) ARX_HIP(hipEventRecord(w.ev1, r->stream));
+    if (timed)
+        if (const arx_status te = w.timer.end(r->stream); te != ARX_OK) return te;
     if (const arx_status d = fif_done_conv(r); d != ARX_OK) return d;
     ARX_HIP(hipStreamSynchronize(r->stream));
-    if (ms) {
-        float el = 0.0f;
-        ARX_HIP(hipEventElapsedTime(&el, w.ev0, w.ev1));
-        *ms = (double)el;
-    }
+    if (ms)
+        if (const arx_status tm = w.timer.elapsed(ms); tm != ARX_OK) return tm;
     w.state[0] = n_blocks;
     w.state[1] = n_trans;
     w.state[2] = used.size();
@@ -605,8 +600,7 @@ arx_status arx_debug_walk_state(arx_renderer* r, uint64_t out5[5]) {
 
 void arx::free_walk(WalkScratch& w) {
     hipFree(w.d_scratch);
-    if (w.ev0) hipEventDestroy(w.ev0);
-    if (w.ev1) hipEventDestroy(w.ev1);
+    w.timer.destroy();
     const int32_t forced = w.forced_tile;
     w = WalkScratch{};
     w.forced_tile = forced;

@@ -2,8 +2,8 @@
 // (arx_capi.cpp: one renderer's lifecycle, frame sets, timing rings and getters; arx_scene.cpp: the
 // host-only scene image; arx_capi_device_scene.cpp: the tree on the device; arx_capi_trace.cpp: a frame --
 // trace, finalize, analysis; arx_capi_path_cache.cpp: the path cache's buffers and launches;
-// arx_capi_listeners.cpp: a batch of listeners; arx_capi_bands.cpp: frequency bands;
-// arx_capi_listener_bands.cpp: the bands of a batch of listeners; arx_capi_conv.cpp: the
+// arx_capi_listeners.cpp: a batch of listeners and the driver of both batches; arx_capi_bands.cpp: frequency
+// bands; arx_capi_listener_bands.cpp: the bands of a batch of listeners; arx_capi_conv.cpp: the
 // file, live, streaming and walk-through convolution; arx_group.cpp: ray-sharded multi-GPU groups).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 
 #include "../../include/arx.h"
 #include "arx_bands.hpp"
+#include "arx_batch_plan.hpp"
 #include "arx_bvh.hpp"
 #include "arx_kernels.hpp"
 #include "arx_layout.hpp"
@@ -192,62 +193,129 @@ bool grow_device_optional(T** p, uint64_t* cap, uint64_t units, uint64_t bytes, 
     return true;
 }
 
-// A batch of listeners (arx_render_listeners, include/arx.h): the scratch of one chunk -- per listener a
-// candidate list with its heads, a table entry, a histogram, a counter block, a candidate tally, three
-// analysis results and an f32 IR pair; then one decay-curve buffer and the analysis kernels' scratch --
-// in one allocation made by the first batched call, kept across calls and freed when it must grow and at
-// arx_destroy; outside the path cache's cap.  The chunk's receiver slots live in the renderer's node and
-// triangle arrays (listener_layout, arx_layout.hpp), which the first batched call widens.
-struct ListenerBatch {
-    int32_t forced_chunk = 0;     // arx_debug_set_listener_chunk: 0 automatic
+// The device time of one call: an event pair made at first use.  begin and end record on s; elapsed waits
+// for the end event.  Each call keeps its own rule for when it is timed and where its end lies.
+struct CallTimer {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    arx_status begin(hipStream_t s) {
+        if (!ev0) ARX_HIP(hipEventCreate(&ev0));
+        if (!ev1) ARX_HIP(hipEventCreate(&ev1));
+        ARX_HIP(hipEventRecord(ev0, s));
+        return ARX_OK;
+    }
+    arx_status end(hipStream_t s) {
+        ARX_HIP(hipEventRecord(ev1, s));
+        return ARX_OK;
+    }
+    arx_status elapsed(double* ms) {
+        float t = 0.0f;
+        ARX_HIP(hipEventSynchronize(ev1));
+        ARX_HIP(hipEventElapsedTime(&t, ev0, ev1));
+        if (ms) *ms = (double)t;
+        return ARX_OK;
+    }
+    void destroy() {
+        if (ev0) hipEventDestroy(ev0);
+        if (ev1) hipEventDestroy(ev1);
+        ev0 = ev1 = nullptr;
+    }
+};
+
+// What a batch of listeners owns (arx_render_listeners: arx_renderer::listeners; arx_render_listener_bands:
+// arx_renderer::listener_bands; include/arx.h): the scratch of one chunk (batch_scratch, arx_batch_plan.hpp)
+// in one allocation made by the first batched call, reused while it is large enough, freed when it must grow
+// and at arx_destroy, outside the path cache's cap; and the call's pinned block (batch_pinned).  The chunk's
+// receiver slots live in the renderer's node and triangle arrays (listener_layout, arx_layout.hpp), which the
+// first batched call widens.
+struct ListenerScratch {
+    int32_t forced_chunk = 0;     // arx_debug_set_listener_chunk: 0 automatic (`listeners` holds it for both calls)
     void* d_scratch = nullptr;
     uint64_t scratch_bytes = 0;
-    int32_t chunk = 0;            // listeners the scratch was laid out for ...
-    uint64_t rays = 0;            // ... at this many rays ...
-    int32_t ir_len = 0;           // ... and this IR length
     uint64_t no_room = 0;         // > 0: a scratch of this size did not fit on the device: not tried again
-    void* h_pinned = nullptr;     // per listener of a call: its table entry, counters, tally and results
-    size_t h_listeners = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+    void* h_pinned = nullptr;     // per listener of a call: its table entry, counter words and results
+    size_t h_bytes = 0;
+    void* d_filters = nullptr;    // the band call's filter bank (n_bands x taps f64)
+    uint64_t filters_cap = 0;     // bytes
+    CallTimer timer;
 };
-constexpr uint64_t kListenerBudget = 512ull << 20;  // scratch of an automatic chunk
-void free_listener_batch(ListenerBatch& b);
-// What a chunk of receiver slots is laid out from (arx_capi_listeners.cpp; shared with
-// arx_capi_listener_bands.cpp): the receiver's and the renderer's own tree sizes, and the chunk.
+void free_listener_scratch(ListenerScratch& b);  // forced_chunk survives
+// What a chunk of receiver slots is laid out from: the receiver's and the renderer's own tree sizes, and the chunk.
 struct ListenerSlots {
     int64_t recv_nodes = 0, recv_tris = 0, own_nodes = 0, own_tris = 0;
     int32_t chunk = 0;
     ListenerLayout layout(int32_t slot) const;
 };
-ListenerSlots listener_slots(const arx_renderer* r);  // chunk left 0
-// bytes of one slot in the node and triangle arrays: its nodes (64-B and 32-B), triangle records and top node
-uint64_t listener_slot_bytes(int64_t recv_nodes, int64_t recv_tris);
-// The quantization grid grown once, if need be, to hold the receivers of poses [first, n).
-arx_status listener_grid_for(arx_renderer* r, const arx_listener_pose* poses, size_t first, size_t n);
-// The tree extended by s.chunk slots passes the kernels' offset limits and the structural check.
-bool listener_slots_valid(const arx_renderer* r, const ListenerSlots& s);
-// A pose the batched kernels take: the emitter outside its receiver box grown by the filter's margin
-// fgrow, and its receiver on the grid.
-bool listener_pose_batchable(const arx_renderer* r, const arx_listener_pose& p, float fgrow);
-// A table entry's pose and slot (centre, top node, the refit's rotation, padding and shifts); its pointers zeroed.
-void listener_entry_place(const arx_renderer* r, const ListenerSlots& s, int32_t slot, const arx_listener_pose& p,
-                          ListenerEntry* e);
-// A batch of listeners per band (arx_render_listener_bands, include/arx.h): one scratch allocation -- the
-// call's per-ray band counts and base counter block, then per listener of a chunk what ListenerBatch holds
-// with a bands' block for the histogram, the counters, the results and the IRs, and a broadband IR pair --
-// made by the first batched call, kept across calls, freed when it must grow and at arx_destroy; outside
-// the path cache's cap.  The chunk size is ListenerBatch::forced_chunk's or automatic.
-struct ListenerBandBatch {
-    void* d_scratch = nullptr;
-    uint64_t scratch_bytes = 0;
-    uint64_t no_room = 0;         // > 0: a scratch of this size did not fit on the device: not tried again
-    void* d_filters = nullptr;    // the call's filter bank (n_bands x taps f64)
-    uint64_t filters_cap = 0;     // bytes
-    void* h_pinned = nullptr;     // per listener of a call: its table entry, counter blocks and results
-    size_t h_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+// What a replayed frame of the current key would launch, as trace_rays decides it (probe below).
+struct ReplayProbe {
+    bool ready = false;     // the key is recorded with its filter state, and this launch would only replay
+    bool recorded = false;  // the key is recorded (with or without filter state), and this launch would only replay
+    int32_t state = 0;      // what the launch would leave in PathCache::state had it run traced (kPath*)
+    TraceArgs args;         // the replay's arguments (dirs and rec the cache's)
+    const void* planes = nullptr;
 };
-void free_listener_bands(ListenerBandBatch& b);
+// A batched replay's filter arguments: the list and the heads come per listener, from the table.
+inline FilterArgs filter_args(const ReplayProbe& probe, float fgrow) {
+    FilterArgs fa;
+    fa.planes = probe.planes;
+    fa.list = nullptr;
+    fa.heads = nullptr;
+    fa.grow = fgrow;
+    return fa;
+}
+// One call of either batch, for run_listener_call (arx_capi_listeners.cpp): its arguments, what its steps hand
+// each other, and the steps that are the call's own.  bands 0 is arx_render_listeners: its batched listeners
+// are frames of the renderer (`frames`: each counts in ir_generation, the call's last pose is adopted as the
+// renderer's last frame, so that pose's one-listener route waits for the chunks).
+struct ListenerCall {
+    arx_renderer* r;
+    ListenerScratch* own;
+    const arx_listener_pose* poses;
+    size_t n;
+    float* ir_left;               // [pose][cell][ir_len], or null
+    float* ir_right;
+    arx_acoustics* acoustics;     // [pose][cell][3], or null
+    int32_t bands;
+    bool frames, want_ir;
+    // 1. until the key is recorded (with its filter state, where the batch is to run): c.probe, c.first, c.warm
+    arx_status (*warm_up)(ListenerCall& c);
+    // a pose the batch cannot take, through the one-listener calls; sets c.route[j]
+    arx_status (*render_single)(ListenerCall& c, size_t j);
+    // once, in front of the first chunk, when a pose is batched; may be null
+    arx_status (*begin_chunks)(ListenerCall& c);
+    // the chunk's replay launch for the batched poses [c0, c0 + J), refit into d_table's slots
+    arx_status (*replay)(ListenerCall& c, const ListenerEntry* d_table, size_t c0, int32_t J);
+    // after the cells of chunk slot i (pose j) are finalized; may be null
+    arx_status (*finish_listener)(ListenerCall& c, int32_t i, size_t j);
+    // the host-side outputs, after the call's one synchronisation
+    void (*write_outputs)(const ListenerCall& c);
+    uint64_t N = 0;               // rays of a frame
+    size_t ir_len = 0;
+    size_t first = 0;             // poses before it went through the warm-up
+    int32_t warm = 0;             // ordinary launches the recording took
+    std::vector<int32_t> route;   // per pose: ARX_LISTENER_SINGLE or ARX_LISTENER_BATCHED
+    std::vector<size_t> where;    // per pose: its row in the pinned counters / results
+    std::vector<size_t> batched;  // the batched poses, in batched order
+    ListenerEntry* h_entries = nullptr;         // the pinned block (batch_pinned)
+    unsigned long long* h_counters = nullptr;
+    arx_acoustics* h_res = nullptr;
+    unsigned int* h_flag = nullptr;
+    ReplayProbe probe;
+    ListenerSlots sl;             // the receiver slots behind the renderer's own tree; sl.chunk == chunk
+    int32_t chunk = 0;            // listeners per chunk
+    BatchScratch sc{};
+    char* d_base = nullptr;       // the chunk scratch
+    float fgrow = 0.0f;           // the filter's margin on the grid the batch runs on
+    template <class T>
+    T* at(uint64_t offset) const { return reinterpret_cast<T*>(d_base + offset); }
+};
+// arx_render_listeners' and arx_render_listener_bands' common argument checks, in the order the ABI reports
+// them (the plain call passes no filters); ARX_OK for n == 0, which the caller returns as it is.
+arx_status check_batch_args(const arx_renderer* r, const arx_listener_pose* poses, size_t n, const float* ir_left,
+                            const float* ir_right, const double* filters, int32_t taps, const float* bb_left,
+                            const float* bb_right);
+// The call: its pinned block, the driver (warm-up, prepare, select, the one-listener poses, the chunks, the one
+// synchronisation, the off-grid check, the outputs) between the listener saved and restored, and its time.
+arx_status run_listener_call(ListenerCall& c, bool timed, double* ms);
 // The walk-through convolution (arx_convolute_walk, include/arx.h): one scratch allocation per renderer
 // (walk_layout, arx_kernels.hpp), made by the first call, kept across calls and freed when it must grow and
 // at arx_destroy; outside the path cache's cap.
@@ -259,7 +327,7 @@ struct WalkScratch {
     std::vector<double> h_tw;     // their host copy (2 doubles each)
     std::vector<int32_t> h_tables, h_slot;  // a call's item tables and IR slots, reused
     std::vector<double> h_w;      // and its fade weights
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+    CallTimer timer;              // the call's device time
     uint64_t state[5] = {};       // arx_debug_walk_state
 };
 constexpr int32_t kWalkTile = 8;      // items per MAC workgroup
@@ -277,7 +345,7 @@ struct BandState {
     void* d_scratch = nullptr;
     uint64_t scratch_cap = 0;     // bytes of d_scratch
     void* h_pinned = nullptr;     // kMaxBands counter blocks, then kMaxBands x 3 arx_acoustics
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+    CallTimer timer;              // the call's device time
 };
 void free_bands(BandState& b);
 // Band synthesis (arx_combine_bands, include/arx.h): one scratch allocation per renderer (the call's inputs,
@@ -286,17 +354,15 @@ void free_bands(BandState& b);
 struct SynthScratch {
     void* d_scratch = nullptr;
     uint64_t bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // the call's device time
+    CallTimer timer;              // the call's device time
 };
 void free_synth(SynthScratch& s);
-// What a replayed frame of the current key would launch, as trace_rays decides it (probe below).
-struct ReplayProbe {
-    bool ready = false;     // the key is recorded with its filter state, and this launch would only replay
-    bool recorded = false;  // the key is recorded (with or without filter state), and this launch would only replay
-    int32_t state = 0;      // what the launch would leave in PathCache::state had it run traced (kPath*)
-    TraceArgs args;         // the replay's arguments (dirs and rec the cache's)
-    const void* planes = nullptr;
-};
+// A band call's recording (arx_render_bands, arx_render_listener_bands): ordinary launches -- the first at
+// *pose, when one is given -- until the cache holds the key's records (*probe says so); *warm counts them.
+arx_status record_for_bands(arx_renderer* r, uint64_t N, const arx_listener_pose* pose, ReplayProbe* probe, int32_t* warm);
+// One cell -- one histogram -- finalized into its f32 IR pair (want_ir) and analysed into d_res[0..3) (analyse).
+arx_status finalize_and_analyse(arx_renderer* r, const unsigned long long* hist, float* irl, float* irr, arx_acoustics* d_res,
+                                void* edc, void* acou, bool want_ir, bool analyse);
 // Energy of a ray at the emitter (devicePrograms.cu:208).
 float initial_energy(const arx_config& c);
 
@@ -429,11 +495,11 @@ struct arx_renderer {
     int32_t ray_order = ARX_RAY_ORDER_DEFAULT;  // arx_debug_set_ray_order: 0 identity, directions kept; 1 longest-first pool; 2 directions re-made per launch
     uint64_t scene_gen = 0;        // scenes installed (set_scene_image): part of a frame set's OrderKey
     arx::PathCache path_cache;     // scene-only hits of the last repeated key (arx_debug_set_path_cache)
-    arx::ListenerBatch listeners;  // arx_render_listeners' chunk scratch
+    arx::ListenerScratch listeners;  // arx_render_listeners' chunk scratch
     arx::WalkScratch walk;         // arx_convolute_walk's scratch
     arx::BandState bands;          // arx_render_bands' table and scratch
     arx::SynthScratch synth;       // arx_combine_bands' scratch
-    arx::ListenerBandBatch listener_bands;  // arx_render_listener_bands' scratch
+    arx::ListenerScratch listener_bands;  // arx_render_listener_bands' scratch
     arx::QGrid qgrid{};
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)

@@ -6,11 +6,12 @@
 // every query once for several absorption tables (frequency bands); band_base_kernel +
 // band_cand_multi_kernel do the chunk of listeners for every band at once.
 //
-// Every query here is the same arithmetic on the same bits as the traced frame's (the functions of
-// arx_trace_device.hpp), and each step the kernels share -- the kernel set-up, the record read, the
-// receiver query, a candidate's chain, the filter's prelude and its output -- exists once, below.
-// Not part of the trace kernel's identity (build.py TRACE_KERNEL_FILES): an edit here leaves the
-// stored trace profiles valid.
+// Every query here is the same arithmetic on the same bits as the traced frame's (arx_trace_device.hpp's functions),
+// and each step the kernels share -- the kernel set-up, the record read, the receiver query, a candidate's entry,
+// state and chain, the bands' alive mask, the filter's meta plane, box, prelude and output -- exists once, below.
+// Three places keep a copy of their own, because sharing it changed their machine code: receiver_ctx's meta plane,
+// band_replay_kernel's alive update, the two multi kernels' work-item walk.  Not part of the trace kernel's
+// identity (build.py TRACE_KERNEL_FILES): an edit here leaves the stored trace profiles valid.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -74,12 +75,17 @@ __device__ __forceinline__ ReceiverCtx<BLOCK> receiver_ctx(const TraceArgs& a) {
     c.meta = nullptr;
     return c;
 }
+// The filter's per-ray plane, behind the segment and state planes of a recording of n rays.
+__device__ __forceinline__ const unsigned short* filter_meta_plane(const TraceArgs& a, const FilterArgs& f, uint64_t n) {
+    return reinterpret_cast<const unsigned short*>(reinterpret_cast<const float4*>(f.planes) +
+                                                   (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+}
 template <int BLOCK>
 __device__ __forceinline__ ReceiverCtx<BLOCK> receiver_ctx(const TraceArgs& a, const FilterArgs& f) {
     ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a);
     c.seg = reinterpret_cast<const float4*>(f.planes);
     c.state = c.seg + path_filter_seg_rows(a.max_bounces) * c.n;
-    c.meta = reinterpret_cast<const unsigned short*>(c.state + (uint64_t)a.max_bounces * c.n);
+    c.meta = reinterpret_cast<const unsigned short*>(c.state + (uint64_t)a.max_bounces * c.n);  // the meta plane
     return c;
 }
 
@@ -143,7 +149,7 @@ __device__ __forceinline__ void receiver_query(const ReceiverCtx<BLOCK>& c, cons
     best = t.best;
 }
 
-// The path cache's replay (arx_capi_trace.cpp, PathCache): a frame of a key whose scene-only closest
+// The path cache's replay (arx_capi_path_cache.cpp, PathCache): a frame of a key whose scene-only closest
 // hits trace_kernel<RECORD> stored.  A ray's path through the static scene does not depend on the
 // listener; the receiver enters a query only as one more candidate for the closest hit, take_hit's
 // lexicographic minimum of (t, id) does not depend on the order candidates are tested in, and a
@@ -200,6 +206,7 @@ __global__ __launch_bounds__(BLOCK) void replay_kernel(TraceArgs a) {
 // is a scene triangle's, below n_tris (the clamp keeps a bad record inside the table).
 template <int NB>
 __device__ __forceinline__ void band_absorb(const BandArgs& ba, int tri_id, float (&e)[NB]) {
+    static_assert(NB == 4 || NB == 8, "a table row is one or two 16-B loads");
     const uint64_t id = min((uint64_t)(uint32_t)tri_id, (uint64_t)ba.n_tris - 1u);
     const float4* __restrict__ row = reinterpret_cast<const float4*>(ba.table) + id * (NB / 4);
     float tb[NB];
@@ -213,6 +220,16 @@ __device__ __forceinline__ void band_absorb(const BandArgs& ba, int tri_id, floa
     }
 #pragma unroll
     for (int b = 0; b < NB; ++b) e[b] = e[b] * (1.0f - tb[b]);
+}
+
+// The bands that live: the table's at a ray's start; before every query those with e[b] > energy_thres still.
+template <int NB>
+__device__ __forceinline__ uint32_t band_alive_init(int32_t n_bands) { return (1u << min(n_bands, NB)) - 1u; }
+template <int NB>
+__device__ __forceinline__ uint32_t band_alive_update(const float (&e)[NB], float thres, uint32_t alive) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) alive &= (e[b] > thres) ? ~0u : ~(1u << b);
+    return alive;
 }
 
 template <int NB>
@@ -304,7 +321,6 @@ __device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& b
 // replay_kernel on a scene that carries the band's absorption.
 template <int BLOCK, int NB>
 __global__ __launch_bounds__(BLOCK) void band_replay_kernel(TraceArgs a, BandArgs ba) {
-    static_assert(NB == 4 || NB == 8, "a table row is one or two 16-B loads");
     const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a);
     const int lane = threadIdx.x;
     const uint64_t slot = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -322,14 +338,14 @@ __global__ __launch_bounds__(BLOCK) void band_replay_kernel(TraceArgs a, BandArg
     if (slot < c.n) {
         ray_init(a, s, a.ray_begin + slot);
         active = wants_query(a, s);
-        if (active) alive = (1u << min(ba.n_bands, NB)) - 1u;
+        if (active) alive = band_alive_init<NB>(ba.n_bands);
     }
     Ray r;
     Best best;
     while (__ballot(active) != 0ull) {
         if (active) {
 #pragma unroll
-            for (int b = 0; b < NB; ++b) alive &= (e[b] > a.energy_thres) ? ~0u : ~(1u << b);
+            for (int b = 0; b < NB; ++b) alive &= (e[b] > a.energy_thres) ? ~0u : ~(1u << b);  // band_alive_update, in place
             active = alive != 0u;
         }
         if (active) {
@@ -399,11 +415,14 @@ __device__ __forceinline__ bool segment_meets_box(float4 p, float4 q, const floa
     return !(un > uf);
 }
 
+// The receiver's box as the filter takes it: the f32 box of a top node's receiver child (child 1), grown.
+__device__ __forceinline__ void receiver_box(const BvhNode& top, float grow, float (&lo)[3], float (&hi)[3]) {
+    lo[0] = top.b[0] - grow; lo[1] = top.b[2] - grow; lo[2] = top.c[2] - grow;
+    hi[0] = top.b[1] + grow; hi[1] = top.b[3] + grow; hi[2] = top.c[3] + grow;
+}
 // A filter lane's ray: its meta word (0 for an idle lane), the queries it ran, and the wave's longest
 // count, which bounds the segment loop so that every lane's loads stay unconditional.
-struct FilterRay {
-    uint32_t m, count, cmax;
-};
+struct FilterRay { uint32_t m, count, cmax; };
 __device__ __forceinline__ FilterRay filter_ray_prelude(const TraceArgs& a, bool have, uint64_t slot,
                                                         const unsigned short* __restrict__ meta) {
     FilterRay fr;
@@ -486,12 +505,10 @@ __global__ __launch_bounds__(BLOCK) void filter_kernel(TraceArgs a, FilterArgs f
     const bool have = gid < n;
     const uint64_t slot = have ? gid : n - 1;  // n >= 1 (launch_path_replay_filtered); idle lanes read in bounds
     const float4* __restrict__ seg = reinterpret_cast<const float4*>(f.planes);
-    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(
-        seg + (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+    const unsigned short* __restrict__ meta = filter_meta_plane(a, f, n);
     // the receiver's box: the same address for every lane, so scalar loads, once per wave
-    const BvhNode& top = a.cnodes[0];
-    const float lo[3] = {top.b[0] - f.grow, top.b[2] - f.grow, top.c[2] - f.grow};
-    const float hi[3] = {top.b[1] + f.grow, top.b[3] + f.grow, top.c[3] + f.grow};
+    float lo[3], hi[3];
+    receiver_box(a.cnodes[0], f.grow, lo, hi);
     const FilterRay fr = filter_ray_prelude(a, have, slot, meta);
     unsigned long long mask = 0ull;
     float4 p = seg[slot];
@@ -510,6 +527,31 @@ __global__ __launch_bounds__(BLOCK) void filter_kernel(TraceArgs a, FilterArgs f
     filter_store<BLOCK>(mask, ballot, slot, f.list, f.heads, w_cand, w_cq, w_nq);
 }
 
+// What a chain starts from, entry i of `list` for the lanes that `have` one (zeros otherwise): its slot, clamped
+// into the recording; the ray's meta word and count, clamped as the filter clamps it; its mask trimmed to that.
+struct CandEntry { unsigned long long mask; uint64_t slot; uint32_t m, count; };
+template <int BLOCK>
+__device__ __forceinline__ CandEntry cand_entry(const ReceiverCtx<BLOCK>& c, const TraceArgs& a,
+                                                const FilterCand* __restrict__ list, uint64_t i, bool have) {
+    CandEntry ce = {0ull, 0, 0u, 0u};
+    if (have) {
+        const FilterCand e = list[i];
+        ce.mask = e.mask;
+        ce.slot = e.slot < c.n ? e.slot : c.n - 1;
+        ce.m = c.meta[ce.slot];
+    }
+    ce.count = min(ce.m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
+    ce.mask &= ce.count > 0u ? ((1ull << (ce.count - 1u)) << 1) - 1ull : 0ull;  // bits of queries the ray ran
+    return ce;
+}
+// A candidate query's start: the stored state of record `at` (bounce * n + slot) and the cached hit.
+template <int BLOCK>
+__device__ __forceinline__ void cand_state_load(const ReceiverCtx<BLOCK>& c, uint64_t at, RayState& s, Best& best) {
+    const float4 sp = c.seg[at], sd = c.state[at];
+    load_record(c, at, best);
+    s.pos = make_float3(sp.x, sp.y, sp.z); s.dist = sp.w;
+    s.dir = make_float3(sd.x, sd.y, sd.z); s.e = sd.w;
+}
 // One entry of a candidate list, entry i of `list` for the lanes that `have` one: the chain of its
 // queries.  For each set bit, ascending: the stored state and the cached hit, then replay_kernel's
 // query (receiver_query, entered at node `top`) on the same bits with the same functions.  If the receiver
@@ -522,17 +564,7 @@ __device__ __forceinline__ void cand_chain(const ReceiverCtx<BLOCK>& c, const Tr
                                            const FilterCand* __restrict__ list, uint64_t i, bool have, int top,
                                            uint32_t& n_q, uint32_t& n_rx, uint32_t& n_miss) {
     const uint64_t n = c.n;
-    unsigned long long mask = 0ull;
-    uint64_t slot = 0;
-    uint32_t m = 0u;
-    if (have) {
-        const FilterCand e = list[i];
-        mask = e.mask;
-        slot = e.slot < n ? e.slot : n - 1;
-        m = c.meta[slot];
-    }
-    const uint32_t count = min(m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
-    mask &= count > 0u ? ((1ull << (count - 1u)) << 1) - 1ull : 0ull;  // bits of queries the ray ran
+    auto [mask, slot, m, count] = cand_entry(c, a, list, i, have);
     bool active = mask != 0ull, ended = false;
     Ray r;
     Best best;
@@ -543,13 +575,7 @@ __device__ __forceinline__ void cand_chain(const ReceiverCtx<BLOCK>& c, const Tr
         if (active) {
             const uint32_t b = (uint32_t)__builtin_ctzll(mask);
             mask &= mask - 1ull;
-            const uint64_t at = (uint64_t)b * n + slot;
-            const float4 sp = c.seg[at], sd = c.state[at];
-            load_record(c, at, best);
-            s.pos = make_float3(sp.x, sp.y, sp.z);
-            s.dist = sp.w;
-            s.dir = make_float3(sd.x, sd.y, sd.z);
-            s.e = sd.w;
+            cand_state_load(c, (uint64_t)b * n + slot, s, best);
             s.depth = (int)b;
             unit0 = best.unit;
         }
@@ -619,18 +645,13 @@ __global__ __launch_bounds__(BLOCK) void filter_multi_kernel(TraceArgs a, Filter
     const bool have = gid < n;
     const uint64_t slot = have ? gid : n - 1;  // n >= 1 (launch_listeners_replay); idle lanes read in bounds
     const float4* __restrict__ seg = reinterpret_cast<const float4*>(f.planes);
-    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(
-        seg + (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+    const unsigned short* __restrict__ meta = filter_meta_plane(a, f, n);
     const int j0 = (int)blockIdx.y * F;  // this pass's listeners: [j0, min(j0 + F, listeners))
     __shared__ float box[F][6];
     if (threadIdx.x < F) {
         const int i = threadIdx.x;
         float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f};
-        if (j0 + i < listeners) {
-            const BvhNode& top = a.cnodes[tbl[j0 + i].top];  // child 1: the slot's receiver, as the refit left it
-            lo[0] = top.b[0] - f.grow; lo[1] = top.b[2] - f.grow; lo[2] = top.c[2] - f.grow;
-            hi[0] = top.b[1] + f.grow; hi[1] = top.b[3] + f.grow; hi[2] = top.c[3] + f.grow;
-        }
+        if (j0 + i < listeners) receiver_box(a.cnodes[tbl[j0 + i].top], f.grow, lo, hi);  // the slot's, as the refit left it
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             box[i][k] = lo[k];
@@ -742,11 +763,11 @@ __global__ __launch_bounds__(64) void replay_cand_multi_kernel(TraceArgs a, Filt
         const uint32_t base = (word & 15u) * BLOCK;
         const uint4 head = reinterpret_cast<const uint4*>(e.heads)[fb];
         const uint32_t n_cand = min(head.x, kFilterBlock);
+        const uint64_t i = fb * kFilterBlock + base + lane;
         if (base == 0u && lane == 0) {
             n_q += head.z;
             if (head.x) atomicAdd(e.cand, (unsigned long long)head.x);
         }
-        const uint64_t i = fb * kFilterBlock + base + lane;
         cand_chain(c, a, list, i, base + lane < n_cand && i < n, top, n_q, n_rx, n_miss);
     }
     flush_counters(a, n_q, n_rx, n_miss, lane);
@@ -771,14 +792,12 @@ __global__ __launch_bounds__(64) void replay_cand_multi_kernel(TraceArgs a, Filt
 // band (count <= 64), 8 B per ray; the sums go to the base counter block (ba.counters).
 template <int BLOCK, int NB>
 __global__ __launch_bounds__(BLOCK) void band_base_kernel(TraceArgs a, FilterArgs f, BandArgs ba, uint2* __restrict__ counts) {
-    static_assert(NB == 4 || NB == 8, "a table row is one or two 16-B loads");
     const uint64_t n = a.ray_end - a.ray_begin;
     const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool have = gid < n;
     const uint64_t slot = have ? gid : n - 1;  // n >= 1 (launch_band_base); idle lanes read in bounds
     const float4* __restrict__ rec_hit = reinterpret_cast<const float4*>(a.rec);
-    const unsigned short* __restrict__ meta = reinterpret_cast<const unsigned short*>(
-        reinterpret_cast<const float4*>(f.planes) + (path_filter_seg_rows(a.max_bounces) + (uint64_t)a.max_bounces) * n);
+    const unsigned short* __restrict__ meta = filter_meta_plane(a, f, n);
     const FilterRay fr = filter_ray_prelude(a, have, slot, meta);
     float e[NB];
     uint32_t n_q[NB];
@@ -787,10 +806,9 @@ __global__ __launch_bounds__(BLOCK) void band_base_kernel(TraceArgs a, FilterArg
         e[b] = a.e0;
         n_q[b] = 0u;
     }
-    uint32_t alive = fr.count > 0u ? (1u << min(ba.n_bands, NB)) - 1u : 0u;
+    uint32_t alive = fr.count > 0u ? band_alive_init<NB>(ba.n_bands) : 0u;
     for (uint32_t q = 0; q < fr.count; ++q) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) alive &= (e[b] > a.energy_thres) ? ~0u : ~(1u << b);
+        alive = band_alive_update<NB>(e, a.energy_thres, alive);
         if (alive == 0u) break;
 #pragma unroll
         for (int b = 0; b < NB; ++b) n_q[b] += (alive >> b) & 1u;
@@ -824,22 +842,12 @@ __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const Tr
                                            const uint2* __restrict__ counts, uint32_t (&cut)[NB], uint32_t& rx,
                                            uint32_t& miss) {
     const uint64_t n = c.n;
-    unsigned long long mask = 0ull;
-    uint64_t slot = 0;
-    uint32_t m = 0u;
-    if (have) {
-        const FilterCand e = list[i];
-        mask = e.mask;
-        slot = e.slot < n ? e.slot : n - 1;
-        m = c.meta[slot];
-    }
-    const uint32_t count = min(m & (uint32_t)kFilterCount, min(a.max_bounces, kFilterMaxBounces));
-    mask &= count > 0u ? ((1ull << (count - 1u)) << 1) - 1ull : 0ull;  // bits of queries the ray ran
+    auto [mask, slot, m, count] = cand_entry(c, a, list, i, have);
     float e[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) e[b] = a.e0;
     bool active = mask != 0ull;
-    uint32_t alive = active ? (1u << min(ba.n_bands, NB)) - 1u : 0u;
+    uint32_t alive = active ? band_alive_init<NB>(ba.n_bands) : 0u;
     uint32_t q = 0u;  // the bounce the energies stand before
     rx = 0u;
     miss = 0u;
@@ -852,8 +860,7 @@ __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const Tr
         if (active) {
             const uint32_t target = (uint32_t)__builtin_ctzll(mask);
             for (;;) {
-#pragma unroll
-                for (int b = 0; b < NB; ++b) alive &= (e[b] > a.energy_thres) ? ~0u : ~(1u << b);
+                alive = band_alive_update<NB>(e, a.energy_thres, alive);
                 if (alive == 0u || q >= target) break;
                 band_absorb<NB>(ba, __float_as_int(c.rec_hit[(uint64_t)q * n + slot].y), e);
                 ++q;
@@ -861,13 +868,7 @@ __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const Tr
             active = alive != 0u;
         }
         if (active) {
-            const uint64_t at = (uint64_t)q * n + slot;
-            const float4 sp = c.seg[at], sd = c.state[at];
-            load_record(c, at, best);
-            s.pos = make_float3(sp.x, sp.y, sp.z);
-            s.dist = sp.w;
-            s.dir = make_float3(sd.x, sd.y, sd.z);
-            s.e = sd.w;
+            cand_state_load(c, (uint64_t)q * n + slot, s, best);
             s.depth = (int)q;
             unit0 = best.unit;
         }
@@ -903,7 +904,6 @@ __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const Tr
 template <int NB>
 __global__ __launch_bounds__(64) void band_cand_multi_kernel(TraceArgs a, FilterArgs f, const ListenerEntry* __restrict__ tbl,
                                                              BandArgs ba, const uint2* __restrict__ counts) {
-    static_assert(NB == 4 || NB == 8, "a table row is one or two 16-B loads");
     constexpr int BLOCK = 64;
     const ListenerEntry& e = tbl[blockIdx.y];
     const uint64_t n = a.ray_end - a.ray_begin;

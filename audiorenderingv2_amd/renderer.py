@@ -281,25 +281,14 @@ class AudioRenderer:
         array of arx_listener_result's fields, "ms": the call's device time}."""
         P = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 4))
         k = P.shape[0]
-        n = self.ir_length
-        ir = None
-        pl = pr = None
-        if irs is True:
-            ir = (np.zeros((k, n), np.float32), np.zeros((k, n), np.float32))
-            pl, pr = ir[0].ctypes.data, ir[1].ctypes.data
-        elif irs:
-            ir = tuple(irs)
-            pl, pr = (int(getattr(b, "ptr", b)) for b in ir)
+        ir, pl, pr = _ir_pair(irs, (k, self.ir_length))
         ac = (ArxAcoustics * (3 * max(k, 1)))() if acoustics else None
         res = (ArxListenerResult * max(k, 1))()
         ms = C.c_double(0.0)
         check(lib().arx_render_listeners(self.handle, P.ctypes.data_as(C.POINTER(ArxListenerPose)), k, pl, pr, ac, res,
                                          C.byref(ms)))
         stats = np.frombuffer(res, dtype=LISTENER_RESULT_DTYPE, count=k).copy() if k else np.zeros(0, LISTENER_RESULT_DTYPE)
-        out_ac = None
-        if acoustics:
-            out_ac = [{name: _acoustics_dict(ac[3 * j + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)} for j in range(k)]
-        return {"ir": ir, "acoustics": out_ac, "stats": stats, "ms": float(ms.value)}
+        return {"ir": ir, "acoustics": _acoustics_list(ac, k) if acoustics else None, "stats": stats, "ms": float(ms.value)}
 
     def render_bands(self, irs: bool | tuple = False, acoustics: bool = True) -> dict:
         """arx_render_bands: every band of set_band_absorption's table from one walk over the recorded
@@ -309,24 +298,13 @@ class AudioRenderer:
         "sum"}] * B | None, "stats": a structured array of arx_band_result's fields, "ms": the call's
         device time}."""
         k = self.n_bands  # the library's own count: the output buffers are sized from it
-        n = self.ir_length
-        ir = None
-        pl = pr = None
-        if irs is True:
-            ir = (np.zeros((k, n), np.float32), np.zeros((k, n), np.float32))
-            pl, pr = ir[0].ctypes.data, ir[1].ctypes.data
-        elif irs:
-            ir = tuple(irs)
-            pl, pr = (int(getattr(b, "ptr", b)) for b in ir)
+        ir, pl, pr = _ir_pair(irs, (k, self.ir_length))
         ac = (ArxAcoustics * (3 * MAX_BANDS))() if acoustics else None
         res = (ArxBandResult * MAX_BANDS)()
         ms = C.c_double(0.0)
         check(lib().arx_render_bands(self.handle, pl, pr, ac, res, C.byref(ms)))
         stats = np.frombuffer(res, dtype=BAND_RESULT_DTYPE, count=k).copy()
-        out_ac = None
-        if acoustics:
-            out_ac = [{name: _acoustics_dict(ac[3 * j + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)} for j in range(k)]
-        return {"ir": ir, "acoustics": out_ac, "stats": stats, "ms": float(ms.value)}
+        return {"ir": ir, "acoustics": _acoustics_list(ac, k) if acoustics else None, "stats": stats, "ms": float(ms.value)}
 
     def combine_bands(self, irs, filters, n_bands: int | None = None, ir_len: int | None = None, out=None,
                       taps: int | None = None) -> dict:
@@ -419,21 +397,8 @@ class AudioRenderer:
             if g.ndim != 2 or g.shape[0] != nb:
                 raise ValueError(f"filters: a [{nb}, taps] array")
         k, n = P.shape[0], self.ir_length
-        ir = bb = None
-        pl = pr = bl = br = None
-        if irs is True:
-            ir = (np.zeros((k, nb, n), np.float32), np.zeros((k, nb, n), np.float32))
-            pl, pr = ir[0].ctypes.data, ir[1].ctypes.data
-        elif irs:
-            ir = tuple(irs)
-            pl, pr = (int(getattr(b, "ptr", b)) for b in ir)
-        if g is not None:
-            if broadband is None:
-                bb = (np.zeros((k, n), np.float32), np.zeros((k, n), np.float32))
-                bl, br = bb[0].ctypes.data, bb[1].ctypes.data
-            else:
-                bb = tuple(broadband)
-                bl, br = (int(getattr(b, "ptr", b)) for b in bb)
+        ir, pl, pr = _ir_pair(irs, (k, nb, n))
+        bb, bl, br = _ir_pair(g is not None and (True if broadband is None else broadband), (k, n))
         cells = max(k * nb, 1)
         ac = (ArxAcoustics * (3 * cells))() if acoustics else None
         res = (ArxListenerBandResult * cells)()
@@ -445,8 +410,8 @@ class AudioRenderer:
         stats = np.frombuffer(res, dtype=LISTENER_BAND_RESULT_DTYPE, count=k * nb).copy().reshape(k, nb)
         out_ac = None
         if acoustics:
-            out_ac = [[{name: _acoustics_dict(ac[3 * (j * nb + b) + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)}
-                       for b in range(nb)] for j in range(k)]
+            flat = _acoustics_list(ac, k * nb)
+            out_ac = [flat[j * nb:(j + 1) * nb] for j in range(k)]
         return {"ir": ir, "broadband": bb, "acoustics": out_ac, "stats": stats, "ms": float(ms.value)}
 
     def auralise_walk_bands(self, poses, samples, filters, block_frames: int = 4096, crossfade_frames: int | None = None,
@@ -458,19 +423,9 @@ class AudioRenderer:
         P = np.ascontiguousarray(poses, np.float32)
         if P.ndim != 2 or P.shape[1] != 4:
             raise ValueError("poses: a [K, 4] array of (x, y, z, yaw_deg)")
-        x = np.ascontiguousarray(samples, np.float64).reshape(-1)
-        B = int(block_frames)
-        F = B if crossfade_frames is None else int(crossfade_frames)
-        sched = walk_schedule(x.size, B, self.ir_length, P.shape[0])
-        dev = self.settings.device
-        bufs = [DeviceBuffer(dev, max(P.shape[0] * self.ir_length * 4, 4)) for _ in range(2)]
-        try:
-            rl = self.render_listener_bands(P, irs=False, acoustics=False, filters=filters, broadband=tuple(bufs))
-            res = self.convolute_walk(tuple(bufs), sched, x, B, F, fade, n_irs=P.shape[0])
-        finally:
-            for b in bufs:
-                b.close()
-        return {"out": res["out"], "ir_of_block": sched, "render_ms": rl["ms"], "ms": res["ms"]}
+        return self._auralise(lambda bufs: self.render_listener_bands(P, irs=False, acoustics=False, filters=filters,
+                                                                      broadband=bufs),
+                              P.shape[0], samples, block_frames, crossfade_frames, fade)
 
     def set_walk_tile(self, items: int) -> None:
         """arx_debug_set_walk_tile: items per multiply-accumulate workgroup of convolute_walk (0: the
@@ -534,15 +489,21 @@ class AudioRenderer:
         crossfade_frames=None: a whole block.  Returns {"out": [n_blocks * block_frames, 2] L/R frames,
         "ir_of_block", "render_ms", "ms": the convolution's device time}."""
         P = np.asarray(poses, np.float32).reshape(-1, 4)
+        return self._auralise(lambda bufs: self.render_listeners(P, irs=bufs, acoustics=False), P.shape[0], samples,
+                              block_frames, crossfade_frames, fade)
+
+    def _auralise(self, render, k: int, samples, block_frames: int, crossfade_frames: int | None, fade: str | int) -> dict:
+        """Both auralise_walk methods: render(a pair of device buffers of k * ir_len floats each) fills them with
+        the k poses' IRs, then convolute_walk runs on them with the poses spread evenly over the input's blocks."""
         x = np.ascontiguousarray(samples, np.float64).reshape(-1)
         B = int(block_frames)
         F = B if crossfade_frames is None else int(crossfade_frames)
-        sched = walk_schedule(x.size, B, self.ir_length, P.shape[0])
+        sched = walk_schedule(x.size, B, self.ir_length, k)
         dev = self.settings.device
-        bufs = [DeviceBuffer(dev, max(P.shape[0] * self.ir_length * 4, 4)) for _ in range(2)]
+        bufs = [DeviceBuffer(dev, max(k * self.ir_length * 4, 4)) for _ in range(2)]
         try:
-            rl = self.render_listeners(P, irs=tuple(bufs), acoustics=False)
-            res = self.convolute_walk(tuple(bufs), sched, x, B, F, fade, n_irs=P.shape[0])
+            rl = render(tuple(bufs))
+            res = self.convolute_walk(tuple(bufs), sched, x, B, F, fade, n_irs=k)
         finally:
             for b in bufs:
                 b.close()
@@ -747,6 +708,24 @@ def _acoustics_dict(a: ArxAcoustics) -> dict:
     return d
 
 
+def _acoustics_list(ac, cells: int) -> list:
+    """cells x 3 arx_acoustics as [{"left", "right", "sum"}] * cells."""
+    return [{name: _acoustics_dict(ac[3 * j + c]) for c, name in enumerate(ACOUSTICS_CHANNELS)} for j in range(cells)]
+
+
+def _ir_pair(irs, shape) -> tuple:
+    """A method's irs argument -- False, True (host arrays of `shape`) or a pair of DeviceBuffers / device
+    pointers -- as (what the method returns, the left pointer, the right pointer)."""
+    if irs is True:
+        ir = (np.zeros(shape, np.float32), np.zeros(shape, np.float32))
+        return ir, ir[0].ctypes.data, ir[1].ctypes.data
+    if irs:
+        ir = tuple(irs)
+        pl, pr = (int(getattr(b, "ptr", b)) for b in ir)
+        return ir, pl, pr
+    return None, None, None
+
+
 def acoustics_from_histogram(left, right, sample_rate: int, unit: float = 1.0) -> dict:
     """arx_acoustics_from_histogram (host only, no device): the parameters of an int64 histogram
     pair by the definitions of include/arx.h, as {"left": ..., "right": ..., "sum": ...}."""
@@ -758,15 +737,13 @@ def acoustics_from_histogram(left, right, sample_rate: int, unit: float = 1.0) -
     P = C.POINTER(C.c_int64)
     check(lib().arx_acoustics_from_histogram(L.ctypes.data_as(P), R.ctypes.data_as(P), L.size, int(sample_rate),
                                              float(unit), out))
-    return {name: _acoustics_dict(out[i]) for i, name in enumerate(ACOUSTICS_CHANNELS)}
+    return _acoustics_list(out, 1)[0]
 
 
 def write_acoustics_json(path: str, channels: dict) -> None:
     """{"left" | "right" | "sum": acoustics()} as JSON: invalid quantities (NaN) as null, an infinite
     clarity as the string "inf", valid as a sorted list."""
-    with open(path, "w") as fh:
-        json.dump({ch: {k: _json_plain(v) for k, v in a.items()} for ch, a in channels.items()}, fh, indent=1)
-        fh.write("\n")
+    _dump_json(path, _channels_plain(channels))
 
 
 def _json_plain(v):
@@ -776,6 +753,16 @@ def _json_plain(v):
     if isinstance(v, float) and not np.isfinite(v):
         return None if np.isnan(v) else ("inf" if v > 0 else "-inf")
     return list(v) if isinstance(v, tuple) else v
+
+
+def _channels_plain(channels: dict) -> dict:
+    return {ch: {k: _json_plain(v) for k, v in a.items()} for ch, a in channels.items()}
+
+
+def _dump_json(path: str, obj) -> None:
+    with open(path, "w") as fh:
+        json.dump(obj, fh, indent=1)
+        fh.write("\n")
 
 
 LISTENER_RESULT_DTYPE = np.dtype([("queries", "<u8"), ("receiver_hits", "<u8"), ("misses", "<u8"), ("candidate_rays", "<u8"),
@@ -802,11 +789,8 @@ def write_band_acoustic_map_json(path: str, poses, bands_hz, acoustics: list) ->
         if len(bands_hz) != len(per_band):
             raise ValueError(f"{len(bands_hz)} bands, {len(per_band)} results")
         out.append({"pose": [float(v) for v in p],
-                    "bands": [{"band_hz": float(hz), **{ch: {k: _json_plain(v) for k, v in vals.items()} for ch, vals in a.items()}}
-                              for hz, a in zip(bands_hz, per_band)]})
-    with open(path, "w") as fh:
-        json.dump(out, fh, indent=1)
-        fh.write("\n")
+                    "bands": [{"band_hz": float(hz), **_channels_plain(a)} for hz, a in zip(bands_hz, per_band)]})
+    _dump_json(path, out)
 
 
 def write_band_acoustics_json(path: str, bands_hz, acoustics: list) -> None:
@@ -814,11 +798,7 @@ def write_band_acoustics_json(path: str, bands_hz, acoustics: list) -> None:
     write_acoustics_json writes them."""
     if len(bands_hz) != len(acoustics):
         raise ValueError(f"{len(bands_hz)} bands, {len(acoustics)} results")
-    out = [{"band_hz": float(hz), **{ch: {k: _json_plain(v) for k, v in vals.items()} for ch, vals in a.items()}}
-           for hz, a in zip(bands_hz, acoustics)]
-    with open(path, "w") as fh:
-        json.dump(out, fh, indent=1)
-        fh.write("\n")
+    _dump_json(path, [{"band_hz": float(hz), **_channels_plain(a)} for hz, a in zip(bands_hz, acoustics)])
 
 
 def octave_crossovers(centres_hz) -> np.ndarray:
@@ -862,10 +842,7 @@ def write_acoustic_map_json(path: str, poses, acoustics: list) -> None:
     P = np.asarray(poses, np.float32).reshape(-1, 4)
     if P.shape[0] != len(acoustics):
         raise ValueError("one acoustics entry per pose")
-    with open(path, "w") as fh:
-        json.dump([{"pose": [float(v) for v in p], **{ch: {k: _json_plain(v) for k, v in a.items()} for ch, a in ac.items()}}
-                   for p, ac in zip(P, acoustics)], fh, indent=1)
-        fh.write("\n")
+    _dump_json(path, [{"pose": [float(v) for v in p], **_channels_plain(ac)} for p, ac in zip(P, acoustics)])
 
 
 def edc_from_histogram(hist) -> np.ndarray:

@@ -362,6 +362,21 @@ def test_chunking_gives_the_same_bits(conference, conf_auto, chunk):
         r.close()
 
 
+def test_three_calls_of_different_chunks_on_one_renderer(loops):
+    """The scratch is reused by its size: forced chunks 2, then 4 (it grows), then 1 (reused larger than needed)
+    on one renderer, the four box poses each time, every call against the loop."""
+    want = loops.want("box4", lambda: box_renderer(4), BOX_POSES)
+    r = box_renderer()
+    try:
+        for chunk in (2, 4, 1):
+            r.set_listener_chunk(chunk)
+            out = call(r, BOX_POSES)
+            assert routes(out) == [BATCHED, BATCHED, BATCHED, SINGLE]
+            same_cells(out["cells"], want, f"chunk {chunk}")
+    finally:
+        r.close()
+
+
 SETTINGS = [("no-threshold", False, dict(energy_thres=0.0)), ("threshold", False, dict(energy_thres=thres(BOX_RAYS, 0.2))),
             ("mono", False, dict(mono=True)), ("hrtf-0.25", False, dict(hrtf_absorption_rate=0.25)), ("marked", True, {})]
 

@@ -154,6 +154,24 @@ def test_box_scene_two_listeners(refs):
         r.close()
 
 
+def test_three_calls_of_different_chunks_on_one_renderer(refs):
+    """The scratch is reused by its size: forced chunks 2, then 4 (it grows), then 1 (reused larger than needed)
+    on one renderer, four box poses each time, every call against the loop."""
+    scene = box_scene()
+    poses = BOX_POSES + [((1.8, 1.3, -0.5), 45.0), ((1.0, 1.5, 0.8), 270.0)]
+    wants = [refs.want(scene, (16, 16, 16), p, emitter=BOX_EMITTER) for p in poses]
+    r = make(scene, (16, 16, 16), True, emitter=BOX_EMITTER, listener=BOX_POSES[0])
+    try:
+        warm_up(r)
+        for chunk in (2, 4, 1):
+            r.set_listener_chunk(chunk)
+            out = r.render_listeners(arr(poses), irs=True)
+            assert routes(out) == [BATCHED] * 4
+            check(out, wants, f"chunk {chunk}")
+    finally:
+        r.close()
+
+
 LOOP = P[:7] + [P[0]]
 
 
