@@ -17,12 +17,16 @@
 #include <algorithm>
 
 #include "arx_bands.hpp"
+#include "arx_cand_plan.hpp"
 #include "arx_kernels.hpp"
 #include "arx_layout.hpp"
 #include "arx_trace_device.hpp"
 
 #ifndef ARX_REPLAY_BLOCK
 #define ARX_REPLAY_BLOCK 256  // replay_kernel's block; design experiments only (build.py --exp)
+#endif
+#ifndef ARX_CAND_BLOCKS
+#define ARX_CAND_BLOCKS 2048  // replay_cand_kernel's blocks at most; design experiments only (build.py --exp)
 #endif
 
 namespace arx {
@@ -595,34 +599,79 @@ __device__ __forceinline__ void cand_chain(const ReceiverCtx<BLOCK>& c, const Tr
     if (have && !ended) n_q += count;
 }
 
-// replay_cand_kernel: a 64-lane block per 64 entries of each filter block's stretch of the list; the
-// stretch's head says how many it holds (device memory: nothing waits on the host), a lane per
-// candidate ray, each running its entry's chain (cand_chain).  The queries of the rays filter_kernel
-// retired come in through the heads.
+// replay_cand_kernel: the candidate rays' chains (cand_chain), a 64-lane block per part -- 64 entries of a
+// filter block's stretch of the list, a lane per candidate ray -- so a stretch full of candidates is sixteen
+// waves' work, not one wave's sixteen rounds: the pool's slots are ordered longest first with the rays the
+// receiver ended in front (launch_order_pool), so the candidates crowd into a few stretches.  The stretch's
+// head says how many it holds (device memory: nothing waits on the host).
+// Which block takes which part is found from the heads and not by position.  A grid with a block for each of
+// a stretch's sixteen parts is 15 625 blocks at 1 M rays of which a few hundred hold candidates, and such a
+// launch lasts as long as that many blocks take to come and go, whatever they do: 0.20 ms, against 0.10 ms
+// for this one (profiles/r19/ab_cand_blocks.txt).  Here a fixed number of blocks (kCandBlocks) each read all
+// the heads -- 16 B per stretch, kCandHeadsPerLane heads a lane and tile -- and number the parts that hold
+// candidates in stretch order (arx_cand_plan.hpp): block j takes parts j, j + gridDim.x, ...; a block past
+// the last part leaves before anything else is set up.  No list of work items, no device memory and no
+// atomic for it: every block finds its own parts again from the heads.  The queries of the rays
+// filter_kernel retired come in through the heads, tile t's added by block t % gridDim.x.
 __global__ __launch_bounds__(64) void replay_cand_kernel(TraceArgs a, FilterArgs f) {
     constexpr int BLOCK = 64;
-    // Block (fb, c) takes candidates [64 c, 64 c + 64) of filter block fb's stretch, so a stretch full of
-    // candidates is sixteen waves' work, not one wave's sixteen rounds: the pool's slots are ordered
-    // longest first with the rays the receiver ended in front (launch_order_pool), so the candidates
-    // crowd into a few stretches, and a wave per stretch took 0.93 ms at C3 where this takes 0.20.  Most
-    // blocks read their head and leave, before anything else is set up; a stretch's first block stays
-    // to add the head's query count.
     const uint64_t n = a.ray_end - a.ray_begin;
-    const uint32_t chunks = kFilterBlock / BLOCK;
-    const uint64_t fblocks = (n + kFilterBlock - 1) / kFilterBlock;
-    const uint64_t fb = blockIdx.x / chunks;
-    const uint32_t base = (blockIdx.x % chunks) * BLOCK;
-    if (fb >= fblocks) return;
-    const uint4 head = reinterpret_cast<const uint4*>(f.heads)[fb];  // the same address for every lane
-    const uint32_t n_cand = min(head.x, kFilterBlock);
-    if (base > 0u && base >= n_cand) return;
-    const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a, f);
-    const int lane = threadIdx.x;
+    const uint32_t fblocks = (uint32_t)((n + kFilterBlock - 1) / kFilterBlock);  // < 2^27 (launch_path_replay_filtered)
+    const uint4* __restrict__ heads = reinterpret_cast<const uint4*>(f.heads);
+    const uint32_t lane = threadIdx.x;
     uint32_t n_q = 0, n_rx = 0, n_miss = 0;
-    if (base == 0u && lane == 0) n_q += head.z;
-    const uint64_t i = fb * kFilterBlock + base + lane;
-    cand_chain(c, a, f.list, i, base + lane < n_cand && i < n, 0, n_q, n_rx, n_miss);
-    flush_counters(a, n_q, n_rx, n_miss, lane);
+    // how many parts there are, and this block's share of the heads' query counts
+    uint32_t items = 0u;
+    for (uint32_t t0 = 0u, t = 0u; t0 < fblocks; t0 += kCandTile, ++t) {
+        const bool add = t % gridDim.x == blockIdx.x;
+#pragma unroll
+        for (uint32_t i = 0; i < kCandHeadsPerLane; ++i) {
+            const uint32_t fb = t0 + lane * kCandHeadsPerLane + i;
+            if (fb < fblocks) {
+                const uint4 h = heads[fb];
+                items += cand_parts(min(h.x, kFilterBlock));
+                if (add) n_q += h.z;
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) items += (uint32_t)__shfl_xor((int)items, off, 64);
+    items = (uint32_t)__builtin_amdgcn_readfirstlane((int)items);
+    if (blockIdx.x >= items) {
+        flush_counters(a, n_q, 0u, 0u, threadIdx.x);
+        return;
+    }
+    const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a, f);
+    uint32_t k = blockIdx.x, done = 0u;  // the block's next part; the parts of the tiles before this one
+    for (uint32_t t0 = 0u; t0 < fblocks && k < items; t0 += kCandTile) {
+        uint32_t cand[kCandHeadsPerLane], parts = 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < kCandHeadsPerLane; ++i) {
+            const uint32_t fb = t0 + lane * kCandHeadsPerLane + i;
+            cand[i] = fb < fblocks ? min(heads[fb].x, kFilterBlock) : 0u;
+            parts += cand_parts(cand[i]);
+        }
+        uint32_t incl = parts;  // inclusive scan within the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t v = (uint32_t)__shfl_up((int)incl, off, 64);
+            if (lane >= (uint32_t)off) incl += v;
+        }
+        const uint32_t tile_parts = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        while (k < done + tile_parts) {  // part k lies in this tile: the first lane whose scan passes it holds it
+            const uint32_t r = k - done;
+            const int owner = __builtin_ctzll(__ballot(incl > r));
+            const CandItem it = cand_lane_item(cand, r - (incl - parts));  // the owner's is the part
+            const uint32_t fb = min(t0 + (uint32_t)owner * kCandHeadsPerLane + (uint32_t)__shfl((int)it.head, owner, 64), fblocks - 1u);
+            const uint32_t base = (uint32_t)__shfl((int)it.part, owner, 64) * kCandPart;
+            const uint32_t n_cand = (uint32_t)__shfl((int)it.n_cand, owner, 64);
+            const uint64_t i = (uint64_t)fb * kFilterBlock + base + lane;
+            cand_chain(c, a, f.list, i, base + lane < n_cand && i < n, 0, n_q, n_rx, n_miss);
+            k += gridDim.x;
+        }
+        done += tile_parts;
+    }
+    flush_counters(a, n_q, n_rx, n_miss, threadIdx.x);
 }
 
 // ------------------------------------------------- a batch of listeners ---
@@ -694,10 +743,11 @@ __global__ __launch_bounds__(BLOCK) void filter_multi_kernel(TraceArgs a, Filter
 
 // cand_work_kernel, a block per listener: the listener's work items in stretch order -- for every stretch
 // its first 64 entries (that item also adds the stretch's head) and every further 64 that hold a
-// candidate -- as (stretch * 16 + part) words behind their count (ListenerEntry::work).  replay_cand_kernel
-// launches a block for each of a frame's 16 x stretches parts and lets the empty ones leave; with a chunk
-// of listeners those are hundreds of thousands of blocks that only read a head, and dispatching them was
-// what the chunk's candidate launch took (profiles/r12/listeners_kernel_stats.csv).  No atomic: a block-wide
+// candidate -- as (stretch * 16 + part) words behind their count (ListenerEntry::work).  A block for
+// each of a frame's 16 x stretches parts, the empty ones leaving, is with a chunk of listeners hundreds of
+// thousands of blocks that only read a head, and dispatching them was what the chunk's candidate launch took
+// (profiles/r12/listeners_kernel_stats.csv; one frame's replay_cand_kernel finds its parts from the heads in
+// every block, with no list, for the same reason).  No atomic: a block-wide
 // scan of the parts per stretch, tile after tile.
 __global__ __launch_bounds__(1024) void cand_work_kernel(const ListenerEntry* __restrict__ tbl, uint32_t fblocks) {
     constexpr int BLOCK = 1024, WAVES = BLOCK / 64;
@@ -993,6 +1043,8 @@ hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, 
     if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.hist || !a.counters || !a.rec || !a.cnodes || !f.planes ||
         !f.list || !f.heads || a.max_bounces < 1 || a.max_bounces > kFilterMaxBounces)
         return hipErrorInvalidValue;
+    // (the clear folded into filter_kernel's lanes, as the direction pre-pass does it for a traced frame, took
+    // the launch away and cost 4 % of the step: profiles/r19/ab_cand_blocks.txt)
     if (a.clear_bins > 0 || a.clear_counters > 0) {
         const hipError_t e = launch_clear(a.hist, a.clear_bins, a.counters, a.clear_counters, s);
         if (e != hipSuccess) return e;
@@ -1000,11 +1052,14 @@ hipError_t launch_path_replay_filtered(const TraceArgs& a, const FilterArgs& f, 
     constexpr int FB = (int)kFilterBlock;
     const uint64_t n_rays = a.ray_end - a.ray_begin;
     const uint64_t fblocks = (n_rays + FB - 1) / FB;
-    // a wave per 64 entries of every filter block's stretch of the list
+    // the candidate launch: a wave per 64 entries of a stretch at most, and a fixed number of blocks.  2 048:
+    // at 1 M rays 1 024 and 2 048 are even and 4 096 is 4 % slower; with a fifth of the rays candidates
+    // (over 3 300 parts) 1 024 is 40 % slower than 2 048 and 4 096 is 3 % faster (profiles/r19/ab_cand_blocks.txt)
+    constexpr uint64_t kCandBlocks = ARX_CAND_BLOCKS;
     const uint64_t g2 = fblocks * (FB / 64);
     if (g2 > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(filter_kernel<FB>, dim3((unsigned)fblocks), dim3(FB), 0, s, a, f);
-    hipLaunchKernelGGL(replay_cand_kernel, dim3((unsigned)g2), dim3(64), 0, s, a, f);
+    hipLaunchKernelGGL(replay_cand_kernel, dim3((unsigned)std::min<uint64_t>(g2, kCandBlocks)), dim3(64), 0, s, a, f);
     return hipGetLastError();
 }
 
