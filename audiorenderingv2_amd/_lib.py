@@ -208,6 +208,14 @@ SIGNATURES = {
     "arx_render_listener_bands": (C.c_int, [_P, C.POINTER(ArxListenerPose), C.c_size_t, _P, _P, _P, C.c_int32, _P, _P,
                                             C.POINTER(ArxAcoustics), C.POINTER(ArxListenerBandResult), _D]),
     "arx_debug_listener_band_bytes": (C.c_uint64, [C.c_uint64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "arx_set_source_directivity": (C.c_int, [_P, _F, C.c_int32, C.c_int32]),
+    "arx_set_source_orientation": (C.c_int, [_P, _F]),
+    "arx_source_directivity_bands": (C.c_int32, [_P]),
+    "arx_directivity_gains_host": (C.c_int, [_F, C.c_int32, C.c_int32, _F, _F, C.c_uint64, C.c_int32, _F]),
+    "arx_debug_directivity_plane": (C.c_int, [_P, C.c_uint64, C.c_uint64, _F]),
+    "arx_debug_directivity_bytes": (C.c_uint64, [C.c_uint64, C.c_int32, C.c_int32]),
+    "arx_debug_directivity_planes_made": (C.c_uint64, [_P]),
+    "arx_debug_band_histograms": (C.c_int, [_P, _I64, C.c_size_t]),
     "arx_debug_set_trace_path": (C.c_int, [_P, C.c_int]),
     "arx_debug_set_refit_pad": (C.c_int, [_P, C.c_float]),
     "arx_debug_check_tree_limits": (C.c_int, [C.c_uint64, C.c_uint64]),

@@ -25,8 +25,12 @@ struct BandArgs {
     int64_t n_tris;                // rows of the table (the scene's input triangles), >= 1
     int32_t n_bands;               // 1 .. kMaxBands
     int32_t pad;
+    // Source directivity (arx_directivity.hpp): the gain plane [slot][band_width(n_bands)] of the recording's
+    // rays, or null.  With a plane the launchers take the kernels' DIRECTED instantiations, in which a ray's
+    // band b starts from e0 * gain[slot][b]; without one, the instantiations that never read this field.
+    const float* gain;
 };
-static_assert(sizeof(BandArgs) == 40, "BandArgs: a kernel parameter behind TraceArgs");
+static_assert(sizeof(BandArgs) == 48, "BandArgs: a kernel parameter behind TraceArgs");
 
 // The scratch of a call for n_bands bands, as byte offsets (every region 16-B aligned): per band a
 // histogram, a counter block, three arx_acoustics and an f32 IR pair (the lefts, then the rights); then one

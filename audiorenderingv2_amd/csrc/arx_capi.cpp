@@ -387,6 +387,7 @@ void arx_destroy(arx_renderer* r) {
     free_listener_scratch(r->listeners);
     free_walk(r->walk);
     free_bands(r->bands);
+    free_directivity(r->directivity);
     free_synth(r->synth);
     free_listener_scratch(r->listener_bands);
     if (r->h_tree_flag) hipHostFree(r->h_tree_flag);

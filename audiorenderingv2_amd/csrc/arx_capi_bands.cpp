@@ -200,6 +200,7 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     if (!r->scene_img) return fail(ARX_ERR_NOT_READY, "arx_set_scene has not been called");
     BandState& bs = r->bands;
     if (bs.n_bands < 1) return fail(ARX_ERR_NOT_READY, "arx_set_band_absorption has not been called for this scene");
+    if (const arx_status dst = directivity_check_bands(r, bs.n_bands); dst != ARX_OK) return dst;
     PathCache& pc = r->path_cache;
     if (pc.mode != 1) return fail(ARX_ERR_NOT_READY, "a band render replays the path cache, which is off");
     const uint64_t N = n_rays(r->cfg);
@@ -221,6 +222,7 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     unsigned long long* h_cnt = static_cast<unsigned long long*>(bs.h_pinned);
     arx_acoustics* h_res = reinterpret_cast<arx_acoustics*>(h_cnt + kMaxBands * kBandCounterWords);
     const BandScratchLayout sc = band_scratch_layout(r->ir_len, B);
+    bs.hist_bands = 0;
     if (sc.total > bs.scratch_cap && (st = grow_device(&bs.d_scratch, &bs.scratch_cap, sc.total, 0, 1)) != ARX_OK) return st;
     char* const base = static_cast<char*>(bs.d_scratch);
     unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(base + sc.hist);
@@ -236,6 +238,8 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     ba.counters = d_cnt;
     ba.n_tris = bs.n_tris;
     ba.n_bands = B;
+    // a source pattern: the gain plane of this recording (remade only when stale), and the directed replay
+    if ((st = directivity_plane(r, probe.args.dirs, N, B, &ba.gain)) != ARX_OK) return st;
     ARX_HIP(launch_band_replay(probe.args, ba, r->stream));
     for (size_t b = 0; b < (size_t)B; ++b)
         if ((st = finalize_and_analyse(r, d_hist + b * 2 * ir_len, d_irl + b * ir_len, d_irr + b * ir_len, d_res + 3 * b,
@@ -255,6 +259,8 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     ARX_HIP(hipStreamSynchronize(r->stream));
     if (r->tree_gen != 0 && *r->h_tree_flag == r->tree_gen)
         return fail(ARX_ERR_INTERNAL, "receiver refit / re-quantization: a box left the quantization grid");
+    bs.hist_bands = B;
+    bs.hist_ir_len = r->ir_len;
     for (int32_t b = 0; b < B; ++b) {
         if (results) {
             arx_band_result& o = results[b];
@@ -270,6 +276,19 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
 }
 
 int32_t arx_band_count(const arx_renderer* r) { return r ? r->bands.n_bands : 0; }
+
+arx_status arx_debug_band_histograms(arx_renderer* r, int64_t* h_out, size_t capacity) {
+    if (!r || !h_out) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    const BandState& bs = r->bands;
+    if (bs.hist_bands < 1 || !bs.d_scratch) return fail(ARX_ERR_NOT_READY, "no arx_render_bands call has finished yet");
+    const size_t words = (size_t)bs.hist_bands * 2 * (size_t)bs.hist_ir_len;
+    if (capacity < words) return fail(ARX_ERR_INVALID_ARGUMENT, "the histograms hold %zu words", words);
+    ARX_HIP(hipSetDevice(r->cfg.device));
+    // the last call ended synchronised; its histograms lead the scratch (band_scratch_layout)
+    ARX_HIP(hipMemcpy(h_out, static_cast<const char*>(bs.d_scratch) + band_scratch_layout(bs.hist_ir_len, bs.hist_bands).hist,
+                      words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return ARX_OK;
+}
 
 uint64_t arx_debug_band_bytes(int32_t ir_len, int64_t n_tris, int32_t n_bands) {
     if (ir_len < 0 || n_tris < 0 || n_bands < 1 || n_bands > kMaxBands) return 0;

@@ -61,6 +61,9 @@ BandArgs band_args(const ListenerCall& c) {
     ba.counters = c.at<unsigned long long>(c.sc.base);
     ba.n_tris = c.r->bands.n_tris;
     ba.n_bands = c.bands;
+    // a source pattern: the plane begin_chunks made for this call's recording
+    const DirectivityState& d = c.r->directivity;
+    ba.gain = d.n_bands >= 1 && d.plane_valid ? d.d_plane : nullptr;
     return ba;
 }
 
@@ -72,6 +75,8 @@ arx_status begin_chunks(ListenerCall& lc) {
     if (c.filters)
         ARX_HIP(hipMemcpyAsync(c.own->d_filters, c.filters, (size_t)c.bands * (size_t)c.taps * sizeof(double), hipMemcpyDefault,
                                r->stream));
+    const float* plane = nullptr;  // the gain plane of a source pattern, remade only when stale (band_args reads it)
+    if (const arx_status st = directivity_plane(r, c.probe.args.dirs, c.N, c.bands, &plane); st != ARX_OK) return st;
     ARX_HIP(launch_band_base(c.probe.args, filter_args(c.probe, c.fgrow), band_args(c), c.at<char>(c.sc.counts), r->stream));
     return ARX_OK;
 }
@@ -136,6 +141,7 @@ arx_status arx_render_listener_bands(arx_renderer* r, const arx_listener_pose* p
     if (r->bands.n_bands < 1) return fail(ARX_ERR_NOT_READY, "arx_set_band_absorption has not been called for this scene");
     if (r->path_cache.mode != 1) return fail(ARX_ERR_NOT_READY, "a band render replays the path cache, which is off");
     const int32_t B = r->bands.n_bands;
+    if (const arx_status st = directivity_check_bands(r, B); st != ARX_OK) return st;
     BandCall c{{r, &r->listener_bands, poses, n, ir_left, ir_right, acoustics, B, false, ir_left || filters, warm_up, render_single,
                 begin_chunks, replay, filters ? combine : nullptr, write_outputs},
                filters, filters ? taps : 0, bb_left, bb_right, results};

@@ -74,8 +74,9 @@ void arx::free_path_cache(PathCache& p) {
     for (hipEvent_t e : p.ev_replayed)
         if (e) hipEventDestroy(e);
     const int32_t mode = p.mode, filter_on = p.filter_on;
-    const uint64_t max_bytes = p.max_bytes;
+    const uint64_t max_bytes = p.max_bytes, rec_gen = p.rec_gen;
     p = PathCache{};
+    p.rec_gen = rec_gen;  // never runs backwards: a plane made from freed directions stays stale
     p.mode = mode;
     p.filter_on = filter_on;
     p.max_bytes = max_bytes;
@@ -106,6 +107,8 @@ arx_status issue_path_record(arx_renderer* r, const TraceArgs& pa, uint64_t n_la
     ARX_HIP(launch_path_record(ra, grid_cus, r->stream));
     pc.recorded = true;
     pc.bytes = kPathRecordBytes * (uint64_t)pa.max_bounces * n_launch;
+    pc.rec_rays = n_launch;
+    ++pc.rec_gen;
     pc.rec_stream = r->stream;
     ARX_HIP(hipEventRecord(pc.ev_recorded, r->stream));
     return ARX_OK;

@@ -3,7 +3,8 @@
 // host-only scene image; arx_capi_device_scene.cpp: the tree on the device; arx_capi_trace.cpp: a frame --
 // trace, finalize, analysis; arx_capi_path_cache.cpp: the path cache's buffers and launches;
 // arx_capi_listeners.cpp: a batch of listeners and the driver of both batches; arx_capi_bands.cpp: frequency
-// bands; arx_capi_listener_bands.cpp: the bands of a batch of listeners; arx_capi_conv.cpp: the
+// bands; arx_capi_listener_bands.cpp: the bands of a batch of listeners; arx_capi_directivity.cpp: the
+// source's pattern, its orientation and the gain plane; arx_capi_conv.cpp: the
 // file, live, streaming and walk-through convolution; arx_group.cpp: ray-sharded multi-GPU groups).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -123,6 +124,8 @@ struct PathCache {
     uint64_t cap_bytes = 0;       // of d_hits
     uint64_t dirs_cap = 0;        // rays of d_dirs
     uint64_t bytes = 0;           // of the records in use (recorded)
+    uint64_t rec_rays = 0;        // rays of the records in use
+    uint64_t rec_gen = 0;         // recordings made so far: what was derived from d_dirs is stale once it moves
     uint64_t no_room = 0;         // > 0: records of this size did not fit on the device (treated as over the cap)
     unsigned long long* d_scratch = nullptr;  // the recording's counters and pool cursor (kCursor + 1 words)
     unsigned long long* h_scratch = nullptr;  // pinned, kCounters words
@@ -346,8 +349,37 @@ struct BandState {
     uint64_t scratch_cap = 0;     // bytes of d_scratch
     void* h_pinned = nullptr;     // kMaxBands counter blocks, then kMaxBands x 3 arx_acoustics
     CallTimer timer;              // the call's device time
+    int32_t hist_bands = 0;       // the scratch holds the raw histograms of this many bands (the last call's) ...
+    int32_t hist_ir_len = 0;      // ... of this length (arx_debug_band_histograms)
 };
 void free_bands(BandState& b);
+// Source directivity (arx_set_source_directivity / arx_set_source_orientation, include/arx.h): the pattern's
+// cube map on the device, the orientation, and the gain plane the directed band replays read
+// (arx_directivity.hpp) -- one allocation each, kept across calls, freed when they must grow and at
+// arx_destroy; outside the path cache's cap.  The plane is remade only when a generation word it was made
+// from has moved: the pattern's, the orientation's, the band count or the recording's (PathCache::rec_gen).
+// The pattern survives arx_set_scene and arx_set_band_absorption.
+struct DirectivityState {
+    int32_t n_bands = 0;          // 0: no pattern (the band replays run undirected); 1 serves every band
+    int32_t res = 0;
+    float m[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    float* d_cube = nullptr;
+    uint64_t cube_cap = 0;        // bytes of d_cube
+    float* d_plane = nullptr;
+    uint64_t plane_cap = 0;       // bytes of d_plane
+    uint64_t pattern_gen = 0, orient_gen = 0;
+    bool plane_valid = false;     // d_plane holds the plane of made_*
+    uint64_t made_pattern = 0, made_orient = 0, made_rec = 0, made_rays = 0;
+    int32_t made_bands = 0;
+    uint64_t planes_made = 0;     // gain kernel launches so far
+};
+void free_directivity(DirectivityState& d);
+// The rule of a band call with a pattern installed: a pattern of more than one band matches the table's bands.
+arx_status directivity_check_bands(const arx_renderer* r, int32_t n_bands);
+// The gain plane for a band call of n_bands bands over the recording whose direction copy is `dirs` (n rays),
+// on the renderer's stream: *plane null without a pattern; else the plane, made now if what it was made from
+// has changed.  Nothing of an earlier band call is in flight: each ends synchronised.
+arx_status directivity_plane(arx_renderer* r, const void* dirs, uint64_t n, int32_t n_bands, const float** plane);
 // Band synthesis (arx_combine_bands, include/arx.h): one scratch allocation per renderer (the call's inputs,
 // filters and outputs), made by the first call, kept across calls and freed when it must grow and at
 // arx_destroy; outside the path cache's cap.
@@ -498,6 +530,7 @@ struct arx_renderer {
     arx::ListenerScratch listeners;  // arx_render_listeners' chunk scratch
     arx::WalkScratch walk;         // arx_convolute_walk's scratch
     arx::BandState bands;          // arx_render_bands' table and scratch
+    arx::DirectivityState directivity;  // the source's pattern, orientation and gain plane
     arx::SynthScratch synth;       // arx_combine_bands' scratch
     arx::ListenerScratch listener_bands;  // arx_render_listener_bands' scratch
     arx::QGrid qgrid{};

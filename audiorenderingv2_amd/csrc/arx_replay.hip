@@ -4,7 +4,9 @@
 // the receiver's box (the path filter); filter_multi_kernel + cand_work_kernel +
 // replay_cand_multi_kernel do that for a chunk of listeners in one call; band_replay_kernel replays
 // every query once for several absorption tables (frequency bands); band_base_kernel +
-// band_cand_multi_kernel do the chunk of listeners for every band at once.
+// band_cand_multi_kernel do the chunk of listeners for every band at once.  The band kernels' DIRECTED
+// instantiations start a ray's bands from e0 times its row of a gain plane (a source pattern,
+// arx_directivity.hpp); the others are the kernels as they were, and the launchers take them without a plane.
 //
 // Every query here is the same arithmetic on the same bits as the traced frame's (arx_trace_device.hpp's functions),
 // and each step the kernels share -- the kernel set-up, the record read, the receiver query, a candidate's entry,
@@ -236,6 +238,25 @@ __device__ __forceinline__ uint32_t band_alive_update(const float (&e)[NB], floa
     return alive;
 }
 
+// A directed source (BandArgs::gain, arx_directivity.hpp): the energies a ray's bands start from, e0 times the
+// slot's row of the gain plane -- one or two 16-B loads, once per ray.  Gains lie in [0, 1] and the f32 product
+// by one is monotone, so e[b] <= e0 and the induction above band_replay_kernel holds as it stands: every query a
+// directed band runs has a record.  A band whose start fails e[b] > energy_thres never lives and counts nothing.
+// slot is below the recording's rays (the plane's rows).
+template <int NB>
+__device__ __forceinline__ void band_start_directed(const TraceArgs& a, const BandArgs& ba, uint64_t slot, float (&e)[NB]) {
+    static_assert(NB == 4 || NB == 8, "a plane row is one or two 16-B loads");
+    const float4* __restrict__ row = reinterpret_cast<const float4*>(ba.gain) + slot * (NB / 4);
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) {
+        const float4 g = row[q];
+        e[4 * q + 0] = a.e0 * g.x;
+        e[4 * q + 1] = a.e0 * g.y;
+        e[4 * q + 2] = a.e0 * g.z;
+        e[4 * q + 3] = a.e0 * g.w;
+    }
+}
+
 template <int NB>
 __device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& ba, const float4* __restrict__ tbase,
                                            RayState& s, const Best& best, float (&e)[NB], uint32_t alive,
@@ -323,7 +344,7 @@ __device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& b
 // e[b] never exceeds the recorded ray's energy at the same bounce: a live band's query always has a
 // record.  A lane leaves once no band lives.  Per band the histogram and the three counters are those of
 // replay_kernel on a scene that carries the band's absorption.
-template <int BLOCK, int NB>
+template <int BLOCK, int NB, bool DIRECTED>
 __global__ __launch_bounds__(BLOCK) void band_replay_kernel(TraceArgs a, BandArgs ba) {
     const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a);
     const int lane = threadIdx.x;
@@ -343,6 +364,7 @@ __global__ __launch_bounds__(BLOCK) void band_replay_kernel(TraceArgs a, BandArg
         ray_init(a, s, a.ray_begin + slot);
         active = wants_query(a, s);
         if (active) alive = band_alive_init<NB>(ba.n_bands);
+        if constexpr (DIRECTED) band_start_directed<NB>(a, ba, slot, e);
     }
     Ray r;
     Best best;
@@ -840,7 +862,7 @@ __global__ __launch_bounds__(64) void replay_cand_multi_kernel(TraceArgs a, Filt
 // (the meta word's count, clamped as the filter clamps it), the energies from a.e0 through band_absorb, a
 // band alive -- and counting -- exactly as in band_replay_kernel.  The ray's counts go out packed, a byte per
 // band (count <= 64), 8 B per ray; the sums go to the base counter block (ba.counters).
-template <int BLOCK, int NB>
+template <int BLOCK, int NB, bool DIRECTED>
 __global__ __launch_bounds__(BLOCK) void band_base_kernel(TraceArgs a, FilterArgs f, BandArgs ba, uint2* __restrict__ counts) {
     const uint64_t n = a.ray_end - a.ray_begin;
     const uint64_t gid = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -856,6 +878,7 @@ __global__ __launch_bounds__(BLOCK) void band_base_kernel(TraceArgs a, FilterArg
         e[b] = a.e0;
         n_q[b] = 0u;
     }
+    if constexpr (DIRECTED) band_start_directed<NB>(a, ba, slot, e);
     uint32_t alive = fr.count > 0u ? band_alive_init<NB>(ba.n_bands) : 0u;
     for (uint32_t q = 0; q < fr.count; ++q) {
         alive = band_alive_update<NB>(e, a.energy_thres, alive);
@@ -886,7 +909,7 @@ __global__ __launch_bounds__(BLOCK) void band_base_kernel(TraceArgs a, FilterArg
 // bits per live band, and per band the queries it took away, from the ray's packed counts.  A ray that does
 // not end contributes nothing, and nothing past its last candidate bounce is read.  Wave-wide like
 // receiver_query.
-template <int BLOCK, int NB>
+template <int BLOCK, int NB, bool DIRECTED>
 __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const TraceArgs& a, const BandArgs& ba,
                                            const FilterCand* __restrict__ list, uint64_t i, bool have, int top,
                                            const uint2* __restrict__ counts, uint32_t (&cut)[NB], uint32_t& rx,
@@ -896,6 +919,7 @@ __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const Tr
     float e[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) e[b] = a.e0;
+    if constexpr (DIRECTED) band_start_directed<NB>(a, ba, slot, e);  // cand_entry's slot: clamped into the recording
     bool active = mask != 0ull;
     uint32_t alive = active ? band_alive_init<NB>(ba.n_bands) : 0u;
     uint32_t q = 0u;  // the bounce the energies stand before
@@ -951,7 +975,7 @@ __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const Tr
 // ended rays took away (band_cut_kernel turns them into the frame's count), in words 1 and 2 the frame's
 // receiver hits and misses.  rx and miss are a bit per ray and band: a ballot's population count, summed in
 // scalar registers, lane 0 handing the wave's sum to flush_counters.
-template <int NB>
+template <int NB, bool DIRECTED>
 __global__ __launch_bounds__(64) void band_cand_multi_kernel(TraceArgs a, FilterArgs f, const ListenerEntry* __restrict__ tbl,
                                                              BandArgs ba, const uint2* __restrict__ counts) {
     constexpr int BLOCK = 64;
@@ -979,7 +1003,7 @@ __global__ __launch_bounds__(64) void band_cand_multi_kernel(TraceArgs a, Filter
         if (base == 0u && lane == 0 && head.x) atomicAdd(e.cand, (unsigned long long)head.x);
         const uint64_t i = fb * kFilterBlock + base + lane;
         uint32_t rx, miss;
-        band_chain<BLOCK, NB>(c, a, ba, list, i, base + lane < n_cand && i < n, top, counts, cut, rx, miss);
+        band_chain<BLOCK, NB, DIRECTED>(c, a, ba, list, i, base + lane < n_cand && i < n, top, counts, cut, rx, miss);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             w_rx[b] += (uint32_t)__popcll(__ballot((rx >> b) & 1u));
@@ -1031,10 +1055,16 @@ hipError_t launch_band_replay(const TraceArgs& a, const BandArgs& b, hipStream_t
     constexpr int RB = ARX_REPLAY_BLOCK;
     const uint64_t n_rays = a.ray_end - a.ray_begin;
     const dim3 grid((unsigned)((n_rays + RB - 1) / RB));
-    if (band_width(b.n_bands) == 4)
-        hipLaunchKernelGGL((band_replay_kernel<RB, 4>), grid, dim3(RB), 0, s, a, b);
+    // without a gain plane the instantiations that never read it; with one, the directed ones
+    const bool w4 = band_width(b.n_bands) == 4;
+    if (!b.gain && w4)
+        hipLaunchKernelGGL((band_replay_kernel<RB, 4, false>), grid, dim3(RB), 0, s, a, b);
+    else if (!b.gain)
+        hipLaunchKernelGGL((band_replay_kernel<RB, 8, false>), grid, dim3(RB), 0, s, a, b);
+    else if (w4)
+        hipLaunchKernelGGL((band_replay_kernel<RB, 4, true>), grid, dim3(RB), 0, s, a, b);
     else
-        hipLaunchKernelGGL((band_replay_kernel<RB, 8>), grid, dim3(RB), 0, s, a, b);
+        hipLaunchKernelGGL((band_replay_kernel<RB, 8, true>), grid, dim3(RB), 0, s, a, b);
     return hipGetLastError();
 }
 
@@ -1108,10 +1138,16 @@ hipError_t launch_band_base(const TraceArgs& a, const FilterArgs& f, const BandA
     constexpr int RB = ARX_REPLAY_BLOCK;
     const uint64_t n_rays = a.ray_end - a.ray_begin;
     const dim3 grid((unsigned)((n_rays + RB - 1) / RB));
-    if (band_width(b.n_bands) == 4)
-        hipLaunchKernelGGL((band_base_kernel<RB, 4>), grid, dim3(RB), 0, s, a, f, b, static_cast<uint2*>(counts));
+    uint2* const out = static_cast<uint2*>(counts);
+    const bool w4 = band_width(b.n_bands) == 4;
+    if (!b.gain && w4)
+        hipLaunchKernelGGL((band_base_kernel<RB, 4, false>), grid, dim3(RB), 0, s, a, f, b, out);
+    else if (!b.gain)
+        hipLaunchKernelGGL((band_base_kernel<RB, 8, false>), grid, dim3(RB), 0, s, a, f, b, out);
+    else if (w4)
+        hipLaunchKernelGGL((band_base_kernel<RB, 4, true>), grid, dim3(RB), 0, s, a, f, b, out);
     else
-        hipLaunchKernelGGL((band_base_kernel<RB, 8>), grid, dim3(RB), 0, s, a, f, b, static_cast<uint2*>(counts));
+        hipLaunchKernelGGL((band_base_kernel<RB, 8, true>), grid, dim3(RB), 0, s, a, f, b, out);
     return hipGetLastError();
 }
 
@@ -1122,10 +1158,16 @@ hipError_t launch_listener_bands_replay(const TraceArgs& a, const FilterArgs& f,
     uint64_t per = 0;
     if (const hipError_t e = launch_listeners_filter(a, f, d_table, listeners, s, &per); e != hipSuccess) return e;
     const dim3 grid((unsigned)per, (unsigned)listeners);
-    if (band_width(b.n_bands) == 4)
-        hipLaunchKernelGGL((band_cand_multi_kernel<4>), grid, dim3(64), 0, s, a, f, d_table, b, static_cast<const uint2*>(counts));
+    const uint2* const in = static_cast<const uint2*>(counts);
+    const bool w4 = band_width(b.n_bands) == 4;
+    if (!b.gain && w4)
+        hipLaunchKernelGGL((band_cand_multi_kernel<4, false>), grid, dim3(64), 0, s, a, f, d_table, b, in);
+    else if (!b.gain)
+        hipLaunchKernelGGL((band_cand_multi_kernel<8, false>), grid, dim3(64), 0, s, a, f, d_table, b, in);
+    else if (w4)
+        hipLaunchKernelGGL((band_cand_multi_kernel<4, true>), grid, dim3(64), 0, s, a, f, d_table, b, in);
     else
-        hipLaunchKernelGGL((band_cand_multi_kernel<8>), grid, dim3(64), 0, s, a, f, d_table, b, static_cast<const uint2*>(counts));
+        hipLaunchKernelGGL((band_cand_multi_kernel<8, true>), grid, dim3(64), 0, s, a, f, d_table, b, in);
     hipLaunchKernelGGL(band_cut_kernel, dim3((unsigned)((listeners * b.n_bands + 255) / 256)), dim3(256), 0, s, d_table,
                        b.counters, b.n_bands, listeners);
     return hipGetLastError();

@@ -133,6 +133,51 @@ class AudioRenderer:
         """arx_band_count: the bands of the installed table, 0 without one -- what render_bands returns."""
         return int(lib().arx_band_count(self._h))
 
+    def set_source_directivity(self, cube) -> None:
+        """arx_set_source_directivity: cube (B, 6, res, res) f32 gains in [0, 1] (or (6, res, res): one band,
+        which serves every band of the table); None drops the pattern.  render_bands and
+        render_listener_bands then start ray r's band b from e0 * cube[b][texel of r's direction]; render and
+        render_listeners stay omnidirectional.  The engine does not renormalise: scale base_power by
+        1 / directivity_power(cube) for the omnidirectional source's radiated power."""
+        if cube is None:
+            check(lib().arx_set_source_directivity(self._h, None, 0, 0))
+            return
+        c = _cube_array(cube)
+        check(lib().arx_set_source_directivity(self._h, fptr(c), c.shape[0], c.shape[2]))
+
+    def set_source_orientation(self, yaw_deg=0.0, pitch_deg: float = 0.0, roll_deg: float = 0.0) -> None:
+        """arx_set_source_orientation: the source's local axes in world coordinates -- a 3 x 3 matrix whose
+        rows are the local x, y, z axes, or yaw / pitch / roll in degrees (source_rotation).  Turning costs
+        the gain kernel and a replay, never a trace."""
+        m = np.asarray(yaw_deg, np.float64)
+        m = source_rotation(float(yaw_deg), pitch_deg, roll_deg) if m.ndim == 0 else m
+        m = np.ascontiguousarray(m, np.float32).reshape(-1)
+        if m.size != 9:
+            raise ValueError("source orientation: a 3 x 3 matrix, or yaw, pitch, roll in degrees")
+        check(lib().arx_set_source_orientation(self._h, fptr(m)))
+
+    @property
+    def n_directivity_bands(self) -> int:
+        """arx_source_directivity_bands: the bands of the installed pattern, 0 without one."""
+        return int(lib().arx_source_directivity_bands(self._h))
+
+    def directivity_plane(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """arx_debug_directivity_plane: rows [first, first + count) of the device gain plane, (count, W) f32,
+        indexed like the path cache's direction copy; made from the current recording if it is stale."""
+        bands = self.n_bands or self.n_directivity_bands
+        n = int(self.settings.rays[0]) * int(self.settings.rays[1]) * int(self.settings.rays[2])
+        count = n - first if count is None else count
+        out = np.zeros((count, 4 if bands <= 4 else 8), np.float32)
+        check(lib().arx_debug_directivity_plane(self._h, first, count, fptr(out)))
+        return out
+
+    def band_histograms(self) -> np.ndarray:
+        """arx_debug_band_histograms: the last render_bands call's raw int64 histograms, (B, 2, ir_len):
+        band b's left and right, before finalize."""
+        out = np.zeros((self.n_bands, 2, self.ir_length), np.int64)
+        check(lib().arx_debug_band_histograms(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), out.size))
+        return out
+
     def set_receiver_model(self, left: np.ndarray, right: np.ndarray) -> None:
         for side, t in enumerate((left, right)):
             t = np.ascontiguousarray(t, np.float32).reshape(-1, 9)
@@ -1227,3 +1272,77 @@ def debug_ray_directions(seed: int, first: int, count: int, device: int = 0) -> 
 
 def frac_bits(n_rays: int) -> int:
     return int(lib().arx_frac_bits(n_rays))
+
+
+# -- source directivity (include/arx.h, "Directional sources") ---------------------------------------------
+def _cube_array(cube) -> np.ndarray:
+    """A pattern as (B, 6, res, res) contiguous f32; (6, res, res) is one band."""
+    c = np.ascontiguousarray(cube, np.float32)
+    if c.ndim == 3:
+        c = c[None]
+    if c.ndim != 4 or c.shape[1] != 6 or c.shape[2] != c.shape[3]:
+        raise ValueError("directivity cube: (bands, 6, res, res)")
+    return np.ascontiguousarray(c)
+
+
+def source_rotation(yaw_deg: float = 0.0, pitch_deg: float = 0.0, roll_deg: float = 0.0) -> np.ndarray:
+    """The orientation matrix of set_source_orientation, f64 (3, 3): row i is the source's local axis i in
+    world coordinates.  y is up: yaw turns the source about world +y (counter-clockwise seen from above, so
+    local +x goes from world +x towards world -z), pitch then lifts local +x towards +y about the turned z
+    axis, roll turns about local +x.  All zero is the identity."""
+    y, p, r = np.radians([yaw_deg, pitch_deg, roll_deg])
+    ry = np.array([[np.cos(y), 0.0, np.sin(y)], [0.0, 1.0, 0.0], [-np.sin(y), 0.0, np.cos(y)]])
+    rz = np.array([[np.cos(p), -np.sin(p), 0.0], [np.sin(p), np.cos(p), 0.0], [0.0, 0.0, 1.0]])
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(r), -np.sin(r)], [0.0, np.sin(r), np.cos(r)]])
+    return (ry @ rz @ rx).T  # the columns of the rotation are the local axes: as rows
+
+
+def cube_texel_directions(res: int) -> np.ndarray:
+    """Unit vectors (6, res, res, 3) f64 through the texel centres, in the source's local frame, by the
+    lookup's convention: faces +x, -x, +y, -y, +z, -z; u and v run along the two remaining coordinates in
+    x, y, z order, with no per-face flips."""
+    c = (np.arange(res) + 0.5) * (2.0 / res) - 1.0
+    v, u = np.meshgrid(c, c, indexing="ij")
+    one = np.ones_like(u)
+    faces = [(one, u, v), (-one, u, v), (u, one, v), (u, -one, v), (u, v, one), (u, v, -one)]
+    d = np.stack([np.stack(f, axis=-1) for f in faces])
+    return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+def directivity_cube(fn, res: int, n_bands: int) -> np.ndarray:
+    """A pattern (n_bands, 6, res, res) f32 sampled at the texel centres: fn(d, band) -> gains for unit
+    vectors d (..., 3) in the source's local frame (+x is the source's front)."""
+    d = cube_texel_directions(res)
+    return np.stack([np.asarray(fn(d, b), np.float64) * np.ones(d.shape[:-1]) for b in range(n_bands)]).astype(np.float32)
+
+
+def cardioid_cube(res: int, orders) -> np.ndarray:
+    """Per band ((1 + cos theta) / 2) ** order about local +x: order 0 is omnidirectional, 1 a cardioid,
+    higher orders narrower -- a pattern that narrows with frequency takes ascending orders."""
+    orders = [float(o) for o in np.atleast_1d(orders)]
+    return directivity_cube(lambda d, b: (0.5 * (1.0 + d[..., 0])) ** orders[b], res, len(orders))
+
+
+def directivity_power(cube) -> np.ndarray:
+    """Per band the pattern's mean gain over the sphere, each texel weighted with its exact solid angle:
+    the directed source's radiated power relative to the omnidirectional source's.  The engine does not
+    renormalise; base_power / directivity_power(cube)[b] gives band b the omnidirectional power back."""
+    c = _cube_array(cube).astype(np.float64)
+    res = c.shape[2]
+    e = np.arange(res + 1) * (2.0 / res) - 1.0
+    y, x = np.meshgrid(e, e, indexing="ij")
+    a = np.arctan2(x * y, np.sqrt(x * x + y * y + 1.0))  # the solid angle of [0, x] x [0, y] on the plane z = 1
+    w = a[1:, 1:] - a[:-1, 1:] - a[1:, :-1] + a[:-1, :-1]
+    return (c * w).sum(axis=(1, 2, 3)) / (6.0 * w.sum())
+
+
+def directivity_gains(cube, dirs, orientation=None, width: int | None = None) -> np.ndarray:
+    """arx_directivity_gains_host, the lookup's definition: (n, width) f32 gains of the directions (n, 3)."""
+    c = _cube_array(cube)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    w = (4 if c.shape[0] <= 4 else 8) if width is None else int(width)
+    m = None if orientation is None else np.ascontiguousarray(orientation, np.float32).reshape(-1)
+    out = np.zeros((d.shape[0], max(w, 1)), np.float32)
+    check(lib().arx_directivity_gains_host(fptr(c), c.shape[0], c.shape[2], None if m is None else fptr(m), fptr(d),
+                                           d.shape[0], w, fptr(out)))
+    return out

@@ -970,6 +970,76 @@ arx_status arx_render_listener_bands(arx_renderer* r, const arx_listener_pose* p
 uint64_t arx_debug_listener_band_bytes(uint64_t n_rays, int32_t ir_len, int64_t recv_nodes, int64_t recv_tris,
                                        int32_t n_bands, int32_t listeners);
 
+/* Directional sources: a directivity pattern per band on the band replays.
+ *
+ * A voice, a loudspeaker or an instrument radiates unevenly, more so the higher the band, and can be turned.
+ * A ray's geometry does not depend on its energy, the path cache's records hold the scene-only closest hit
+ * of every query of every ray, and the cache keeps a copy of the rays' initial directions.  So a pattern
+ * changes one thing: the energy a ray's band b starts with, e[b] = e0 * g[ray][b] instead of e0, in the
+ * kernels that already carry one energy per band.  Gains lie in [0, 1] and the f32 product by one is
+ * monotone, so a band's energy still never exceeds the recorded ray's at the same bounce (the argument above
+ * arx_set_band_absorption, now from e0 * g <= e0): every query a directed band runs has a record.  Neither
+ * the pattern nor the orientation is part of any cache key: installing, swapping or turning a pattern costs
+ * one small kernel (the gain plane) and a replay, never a trace and never a scene build.
+ *
+ * The pattern is a cube map per band, cube[((b * 6 + face) * res + v) * res + u], f32 in [0, 1], n_bands 1
+ * (serves every band of the table) or up to ARX_MAX_BANDS, res in [1, 256].  A NaN or a value outside [0, 1]
+ * is ARX_ERR_INVALID_ARGUMENT and arx_last_error() names the band and the texel.  A cube map and not a
+ * latitude / longitude grid because its lookup needs no acos / atan2.
+ *
+ * The lookup is defined on bits: IEEE f32 add, mul, div and comparisons only, in the order written, never
+ * contracted.  arx_directivity_gains_host is that definition in plain C++ and the device runs the same
+ * function.  For a ray's initial direction d and the orientation m (9 floats; row i is the source's local
+ * axis i -- x, y, z -- in world coordinates; identity by default; arx_set_source_orientation checks in f64
+ * that the rows are orthonormal to 1e-5):
+ *   l_i = (m[3i] * d.x + m[3i+1] * d.y) + m[3i+2] * d.z;   ax, ay, az = |l.x|, |l.y|, |l.z|
+ *   ax >= ay && ax >= az:  face = l.x >= 0 ? 0 : 1,  (sc, tc, ma) = (l.y, l.z, ax)
+ *   else ay >= az:         face = l.y >= 0 ? 2 : 3,  (sc, tc, ma) = (l.x, l.z, ay)
+ *   else:                  face = l.z >= 0 ? 4 : 5,  (sc, tc, ma) = (l.x, l.y, az)
+ *   u = sc / ma, v = tc / ma;  iu = min(res - 1, (int)((u + 1.0f) * (0.5f * (float)res))), iv likewise from v
+ *   g[b] = cube[b][face][iv][iu];  ma == 0 (the zero vector; also a NaN): g = 0.
+ * This is the project's own convention: faces +x, -x, +y, -y, +z, -z, and NO per-face sign flips -- on every
+ * face u and v grow with the two remaining local coordinates in x, y, z order.  Nearest texel, no
+ * interpolation.  The engine does not renormalise: gains <= 1 radiate less than the omnidirectional source,
+ * and a caller who wants equal radiated power scales base_power by the pattern's mean gain.
+ *
+ * Who honours it: arx_render_bands and arx_render_listener_bands (one band whose table is the scene's own
+ * absorption is the broadband directed render).  arx_render, arx_render_listeners, the warm launches of the
+ * band calls and renderer groups stay omnidirectional.  With no pattern installed the band calls launch the
+ * same kernel instantiations as before.  At render time a pattern of more than one band must have as many
+ * bands as the table (arx_band_count), else ARX_ERR_INVALID_ARGUMENT.  The pattern and the orientation survive
+ * arx_set_scene and arx_set_band_absorption; n_bands 0 drops the pattern.  A call that fails with
+ * ARX_ERR_INVALID_ARGUMENT or ARX_ERR_NOT_READY changes nothing (a device error while a new pattern is
+ * uploaded drops it).  A band whose start fails e[b] > energy_thres never lives: it counts no query, hit or
+ * miss -- with gain 0 even at energy_thres 0.
+ *
+ * The gain plane g[slot][W] (W = 4 for up to four bands, 8 beyond; the padding 0; slot indexes the cache's
+ * direction copy) is made by the first band call that needs it and remade only when the pattern, the
+ * orientation, the band count or the recording has changed since.  Memory, OUTSIDE arx_debug_set_path_cache's
+ * max_bytes (arx_debug_directivity_bytes): the plane, n_rays x W x 4 B, and the cube, n_bands x 6 x res x res
+ * x 4 B; kept across calls, freed when they must grow and at arx_destroy.  Out of scope: groups, the C++ shim,
+ * app.py modes, interpolated lookup, receiver directivity. */
+arx_status arx_set_source_directivity(arx_renderer* r, const float* cube, int32_t n_bands, int32_t res);
+arx_status arx_set_source_orientation(arx_renderer* r, const float* m9);
+/* bands of the installed pattern: 0 without one (and for a NULL r) */
+int32_t arx_source_directivity_bands(const arx_renderer* r);
+/* host only, the lookup's definition: out[i * width + b] for n directions (x, y, z each); width 4 or 8 and at
+ * least n_bands; a one-band cube fills all `width` columns, else the columns past n_bands are 0; m9 NULL:
+ * identity.  The cube and m9 are checked as the setters check them. */
+arx_status arx_directivity_gains_host(const float* cube, int32_t n_bands, int32_t res, const float* m9,
+                                      const float* dirs_xyz, uint64_t n, int32_t width, float* out);
+/* rows [first_ray, first_ray + count) of the device plane (W floats each, W from the band count the next band
+ * call runs with: the table's, or the pattern's without a table), made now from the current recording if it is
+ * stale.  ARX_ERR_NOT_READY without a pattern or without a recording. */
+arx_status arx_debug_directivity_plane(arx_renderer* r, uint64_t first_ray, uint64_t count, float* h_out);
+/* host only: the formula above (0 for arguments out of range) */
+uint64_t arx_debug_directivity_bytes(uint64_t n_rays, int32_t n_bands, int32_t res);
+/* gain planes made so far (launches of the gain kernel) */
+uint64_t arx_debug_directivity_planes_made(const arx_renderer* r);
+/* the raw fixed-point histograms of the last finished arx_render_bands call, band b's [L | R] at
+ * h_out + b * 2 * ir_len, before finalize; capacity in words.  ARX_ERR_NOT_READY before the first call. */
+arx_status arx_debug_band_histograms(arx_renderer* r, int64_t* h_out, size_t capacity);
+
 /* Walk-through convolution: one signal against a per-block IR schedule, in one call.
  *
  * ir_left / ir_right hold n_irs IRs of ir_len frames each (arx_render_listeners' layout; ir_len and the
