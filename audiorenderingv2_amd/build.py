@@ -33,7 +33,7 @@ CONV_KERNEL_FILES = ("arx_conv_fft.hpp", "arx_conv_kernels.hpp")
 # the trace program (trace_kernel, its pre-pass and launchers), the query's device code and the layouts: the
 # files trace_source_id hashes.  arx_replay.hip, which runs from the trace kernel's records, is not among them
 TRACE_KERNEL_FILES = ("arx_trace.hip", "arx_trace_device.hpp", "arx_layout.hpp")
-HEADERS = ["arx_layout.hpp", "arx_trace_device.hpp", "arx_kernels.hpp", "arx_bands.hpp", "arx_directivity.hpp", "arx_batch_plan.hpp", "arx_cand_plan.hpp", "arx_bvh.hpp", "arx_internal.hpp", "arx_path_plan.hpp", "arx_wide.hpp", "arx_scene_share.hpp",
+HEADERS = ["arx_layout.hpp", "arx_trace_device.hpp", "arx_kernels.hpp", "arx_bands.hpp", "arx_directivity.hpp", "arx_batch_plan.hpp", "arx_cand_plan.hpp", "arx_bvh.hpp", "arx_internal.hpp", "arx_device_mem.hpp", "arx_path_plan.hpp", "arx_wide.hpp", "arx_scene_share.hpp",
            "arx_conv_stream_common.hpp", *CONV_KERNEL_FILES]
 
 COMMON = [

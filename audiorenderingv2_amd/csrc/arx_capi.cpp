@@ -139,35 +139,19 @@ arx_status fif_done_last(arx_renderer* r, FifEvents& ev, int32_t& last) {
 }
 
 // A frame set's stream and buffers, zeroed (the analysis buffers come with the set's first analysis).
-// On a failure the caller frees what was made.
-hipError_t alloc_frame_set(int32_t ir_len, arx_renderer::FrameSet& f) {
+// On a failure the caller releases what was made.
+arx_status alloc_frame_set(int32_t ir_len, arx_renderer::FrameSet& f) {
     const size_t bins = 2 * (size_t)ir_len, words = kCursor + 1;
-    hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipMalloc(&f.d_hist, bins * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMalloc(&f.d_ir, bins * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc(&f.d_counters, words * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipHostMalloc(&f.h_counters, kCounters * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipMemsetAsync(f.d_hist, 0, bins * sizeof(unsigned long long), f.stream)) != hipSuccess ||
-        (e = hipMemsetAsync(f.d_ir, 0, bins * sizeof(float), f.stream)) != hipSuccess ||
-        (e = hipMemsetAsync(f.d_counters, 0, words * sizeof(unsigned long long), f.stream)) != hipSuccess)
-        return e;
-    return hipStreamSynchronize(f.stream);
-}
-
-void free_frame_set(arx_renderer::FrameSet& f) {
-    if (f.stream) hipStreamDestroy(f.stream);
-    hipFree(f.d_hist);
-    hipFree(f.d_ir);
-    hipFree(f.d_counters);
-    hipFree(f.d_dirs);
-    hipFree(f.d_dirs_alt);
-    hipFree(f.d_cost);
-    hipFree(f.d_order_bins);
-    hipFree(f.d_filter_list);
-    if (f.h_counters) hipHostFree(f.h_counters);
-    free_acoustics(f.acou);
-    f = arx_renderer::FrameSet{};
+    arx_status st;
+    ARX_HIP(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
+    if ((st = f.d_hist.reserve(bins)) != ARX_OK || (st = f.d_ir.reserve(bins)) != ARX_OK ||
+        (st = f.d_counters.reserve(words)) != ARX_OK || (st = f.h_counters.reserve(kCounters)) != ARX_OK)
+        return st;
+    ARX_HIP(hipMemsetAsync(f.d_hist.p, 0, f.d_hist.bytes(), f.stream));
+    ARX_HIP(hipMemsetAsync(f.d_ir.p, 0, f.d_ir.bytes(), f.stream));
+    ARX_HIP(hipMemsetAsync(f.d_counters.p, 0, f.d_counters.bytes(), f.stream));
+    ARX_HIP(hipStreamSynchronize(f.stream));
+    return ARX_OK;
 }
 
 arx_status ring_times(arx_renderer* r, const EventRing& ring, double* ms, size_t n, size_t* n_out) {
@@ -177,13 +161,6 @@ arx_status ring_times(arx_renderer* r, const EventRing& ring, double* ms, size_t
 }
 
 }  // namespace
-
-void arx::free_acoustics(arx_renderer::Acoustics& a) {
-    hipFree(a.d_edc);
-    hipFree(a.d_res);
-    hipFree(a.d_scratch);
-    a = arx_renderer::Acoustics{};
-}
 
 arx_status arx::fif_wait_traced(arx_renderer* r) { return fif_wait_all(r, r->ev_traced); }
 arx_status arx::fif_done_traced(arx_renderer* r) { return fif_done_one(r, r->ev_traced); }
@@ -330,10 +307,9 @@ arx_status arx_create(const arx_config* cfg, arx_renderer** out) {
         return s;
     };
     hipError_t e;
-    if ((e = alloc_frame_set(r->ir_len, r->sets[0])) != hipSuccess ||
-        (e = hipMalloc(&r->d_tree_flag, sizeof(unsigned int))) != hipSuccess ||
-        (e = hipHostMalloc(&r->h_tree_flag, sizeof(unsigned int), hipHostMallocDefault)) != hipSuccess)
-        return cleanup(fail(ARX_ERR_HIP, "arx_create: %s", hipGetErrorString(e)));
+    if ((st = alloc_frame_set(r->ir_len, r->sets[0])) != ARX_OK || (st = r->d_tree_flag.reserve(1)) != ARX_OK ||
+        (st = r->h_tree_flag.reserve(1)) != ARX_OK)
+        return cleanup(st);
     r->stream = r->cur().stream;
     // the analysis ring's events are made by the first analyses
     if ((st = r->trace_ring.create_all()) != ARX_OK || (st = r->conv_ring.create_all()) != ARX_OK ||
@@ -350,7 +326,7 @@ arx_status arx_create(const arx_config* cfg, arx_renderer** out) {
     r->stats.trace_waves_target = r->occ[kFmtQ16][0][2];
     r->stats.trace_format = kFmtQ16;
     r->stats.trace_grid_cus = r->cus;
-    if ((e = hipMemsetAsync(r->d_tree_flag, 0, sizeof(unsigned int), r->stream)) != hipSuccess ||
+    if ((e = hipMemsetAsync(r->d_tree_flag.p, 0, sizeof(unsigned int), r->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(r->stream)) != hipSuccess)
         return cleanup(fail(ARX_ERR_HIP, "arx_create: %s", hipGetErrorString(e)));
     *out = r;
@@ -368,33 +344,16 @@ void arx_destroy(arx_renderer* r) {
     r->streams.clear();
     if (r->conv) conv_plan_destroy(r->conv);
     if (r->conv_live) conv_plan_destroy(r->conv_live);
-    hipFree(r->d_live_in);
-    hipFree(r->d_live_out);
-    hipFree(r->d_cnodes);
-    hipFree(r->d_qnodes);
-    hipFree(r->d_tris);
-    hipFree(r->d_gstack);
-    hipFree(r->d_prof);
-    hipFree(r->d_recv_local);
-    hipFree(r->d_recv_nodes);
-    hipFree(r->d_recv_levels);
-    hipFree(r->d_recv_w4);
-    hipFree(r->d_recv_w4_tris);
-    hipFree(r->d_wbuf);
-    hipFree(r->d_w4f);
-    hipFree(r->d_tree_flag);
-    free_path_cache(r->path_cache);
-    free_listener_scratch(r->listeners);
-    free_walk(r->walk);
-    free_bands(r->bands);
-    free_directivity(r->directivity);
-    free_synth(r->synth);
-    free_listener_scratch(r->listener_bands);
-    if (r->h_tree_flag) hipHostFree(r->h_tree_flag);
-    hipFree(r->d_conv_in);
-    hipFree(r->d_conv_out);
+    r->release_buffers();
+    r->path_cache.release();
+    r->listeners.release();
+    r->walk.release();
+    r->bands.release();
+    r->directivity.release();
+    r->synth.release();
+    r->listener_bands.release();
     for (EventRing* ring : {&r->trace_ring, &r->conv_ring, &r->live_ring, &r->analysis_ring}) ring->destroy();
-    for (auto& f : r->sets) free_frame_set(f);
+    for (auto& f : r->sets) f.release();
     delete r;
 }
 
@@ -488,17 +447,16 @@ arx_status arx_set_frames_in_flight(arx_renderer* r, int32_t n) {
     // the path cache's records name the stream that made them and the sets that replayed them
     r->path_cache.recorded = r->path_cache.last_valid = r->path_cache.last_filtered = false;
     for (bool& b : r->path_cache.replayed) b = false;
-    for (int k = n; k < arx_renderer::kMaxFrames; ++k) free_frame_set(r->sets[k]);
+    for (int k = n; k < arx_renderer::kMaxFrames; ++k) r->sets[k].release();
     for (int k = 0; k < n; ++k)
         for (hipEvent_t* e : {&r->ev_traced[k], &r->ev_conv[k], &r->ev_reduced[k], &r->ev_scene[k]})
             if (!*e) ARX_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     for (int k = 1; k < n; ++k) {
         if (r->sets[k].stream) continue;
-        const hipError_t e = alloc_frame_set(r->ir_len, r->sets[k]);
-        if (e != hipSuccess) {
-            for (int q = 1; q < arx_renderer::kMaxFrames; ++q) free_frame_set(r->sets[q]);
+        if (const arx_status se = alloc_frame_set(r->ir_len, r->sets[k]); se != ARX_OK) {
+            for (int q = 1; q < arx_renderer::kMaxFrames; ++q) r->sets[q].release();
             r->fif = 1;
-            return fail(ARX_ERR_HIP, "arx_set_frames_in_flight: %s", hipGetErrorString(e));
+            return se;
         }
     }
     r->fif = n;
@@ -524,8 +482,8 @@ arx_status arx_attach_histogram(arx_renderer* r, int64_t* d_hist, size_t n) {
 
 arx_status arx_ir_device(arx_renderer* r, float** d_left, float** d_right, size_t* ir_len) {
     if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
-    if (d_left) *d_left = r->cur().d_ir;
-    if (d_right) *d_right = r->cur().d_ir + r->ir_len;
+    if (d_left) *d_left = r->cur().d_ir.p;
+    if (d_right) *d_right = r->cur().d_ir.p + r->ir_len;
     if (ir_len) *ir_len = (size_t)r->ir_len;
     return ARX_OK;
 }
@@ -534,7 +492,7 @@ arx_status arx_copy_ir(arx_renderer* r, float* h_left, float* h_right, size_t ir
     if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
     if (ir_len != (size_t)r->ir_len) return fail(ARX_ERR_INVALID_ARGUMENT, "ir_len %zu != %d", ir_len, r->ir_len);
     ARX_HIP(hipSetDevice(r->cfg.device));
-    const float* d_ir = r->cur().d_ir;
+    const float* d_ir = r->cur().d_ir.p;
     if (h_left) ARX_HIP(hipMemcpyAsync(h_left, d_ir, ir_len * sizeof(float), hipMemcpyDeviceToHost, r->stream));
     if (h_right) ARX_HIP(hipMemcpyAsync(h_right, d_ir + r->ir_len, ir_len * sizeof(float), hipMemcpyDeviceToHost, r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));
@@ -545,19 +503,19 @@ arx_status arx_get_stats(arx_renderer* r, arx_stats* out) {
     if (!r || !out) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
     ARX_HIP(hipSetDevice(r->cfg.device));
     const arx_renderer::FrameSet& f = r->cur();
-    ARX_HIP(hipMemcpyAsync(f.h_counters, f.d_counters, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+    ARX_HIP(hipMemcpyAsync(f.h_counters.p, f.d_counters.p, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                            r->stream));
-    ARX_HIP(hipMemcpyAsync(r->h_tree_flag, r->d_tree_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipMemcpyAsync(r->h_tree_flag.p, r->d_tree_flag.p, sizeof(unsigned int), hipMemcpyDeviceToHost, r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));
-    r->stats.queries = f.h_counters[0];
-    r->stats.receiver_hits = f.h_counters[1];
-    r->stats.misses = f.h_counters[2];
+    r->stats.queries = f.h_counters.p[0];
+    r->stats.receiver_hits = f.h_counters.p[1];
+    r->stats.misses = f.h_counters.p[2];
     double ms = 0.0;
     if (r->trace_ring.launches > 0 && r->trace_ring.last_ms(false, &ms) == ARX_OK) r->stats.trace_ms = ms;
     if (r->conv_ring.launches > 0 && r->conv_ring.last_ms(false, &ms) == ARX_OK) r->stats.conv_ms = ms;
     *out = r->stats;
     // the tree as last written (generation tree_gen) has a box off the quantization grid
-    if (r->tree_gen != 0 && *r->h_tree_flag == r->tree_gen)
+    if (r->tree_gen != 0 && *r->h_tree_flag.p == r->tree_gen)
         return fail(ARX_ERR_INTERNAL, "receiver refit / re-quantization: a box left the quantization grid");
     return ARX_OK;
 }

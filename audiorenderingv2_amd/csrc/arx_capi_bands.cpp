@@ -66,12 +66,6 @@ SynthLayout synth_layout(size_t ir_len, int32_t n_bands, int32_t taps) {
 
 }  // namespace
 
-void arx::free_synth(SynthScratch& s) {
-    hipFree(s.d_scratch);
-    s.timer.destroy();
-    s = SynthScratch{};
-}
-
 BandScratchLayout arx::band_scratch_layout(int32_t ir_len, int32_t n_bands) {
     BandScratchLayout s;
     Take take{16};
@@ -84,14 +78,6 @@ BandScratchLayout arx::band_scratch_layout(int32_t ir_len, int32_t n_bands) {
     s.acou = take(acoustics_scratch_bytes());
     s.total = take.at;
     return s;
-}
-
-void arx::free_bands(BandState& b) {
-    hipFree(b.d_table);
-    hipFree(b.d_scratch);
-    if (b.h_pinned) hipHostFree(b.h_pinned);
-    b.timer.destroy();
-    b = BandState{};
 }
 
 arx_status arx::record_for_bands(arx_renderer* r, uint64_t N, const arx_listener_pose* pose, ReplayProbe* probe, int32_t* warm) {
@@ -180,10 +166,9 @@ arx_status arx_set_band_absorption(arx_renderer* r, const float* table, int32_t 
         for (int64_t i = 0; i < n_tris; ++i) rows[(size_t)i * W + k] = table[(int64_t)k * n_tris + i];
     ARX_HIP(hipSetDevice(r->cfg.device));
     bs.n_bands = 0;
-    const uint64_t need = band_table_bytes(n_tris, n_bands);
-    if (need > bs.table_cap)  // no call is in flight: every arx_render_bands ends synchronised
-        if (const arx_status st = grow_device(&bs.d_table, &bs.table_cap, need, 0, 1); st != ARX_OK) return st;
-    ARX_HIP(hipMemcpy(bs.d_table, rows.data(), need, hipMemcpyHostToDevice));
+    // no call is in flight: every arx_render_bands ends synchronised
+    if (const arx_status st = bs.d_table.reserve(rows.size()); st != ARX_OK) return st;
+    ARX_HIP(hipMemcpy(bs.d_table.p, rows.data(), band_table_bytes(n_tris, n_bands), hipMemcpyHostToDevice));
     bs.n_bands = n_bands;
     bs.n_tris = n_tris;
     return ARX_OK;
@@ -216,15 +201,13 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     int32_t warm = 0;
     if ((st = record_for_bands(r, N, nullptr, &probe, &warm)) != ARX_OK) return st;
     // 2. the scratch and the pinned block of the host-side outputs
-    if (!bs.h_pinned)
-        ARX_HIP(hipHostMalloc(&bs.h_pinned, kMaxBands * (kBandCounterWords * 8 + 3 * sizeof(arx_acoustics)),
-                              hipHostMallocDefault));
-    unsigned long long* h_cnt = static_cast<unsigned long long*>(bs.h_pinned);
+    if ((st = bs.h_pinned.reserve(kMaxBands * (kBandCounterWords * 8 + 3 * sizeof(arx_acoustics)))) != ARX_OK) return st;
+    unsigned long long* h_cnt = reinterpret_cast<unsigned long long*>(bs.h_pinned.p);
     arx_acoustics* h_res = reinterpret_cast<arx_acoustics*>(h_cnt + kMaxBands * kBandCounterWords);
     const BandScratchLayout sc = band_scratch_layout(r->ir_len, B);
     bs.hist_bands = 0;
-    if (sc.total > bs.scratch_cap && (st = grow_device(&bs.d_scratch, &bs.scratch_cap, sc.total, 0, 1)) != ARX_OK) return st;
-    char* const base = static_cast<char*>(bs.d_scratch);
+    if ((st = bs.d_scratch.reserve(sc.total)) != ARX_OK) return st;
+    char* const base = bs.d_scratch.p;
     unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(base + sc.hist);
     unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(base + sc.counters);
     arx_acoustics* d_res = reinterpret_cast<arx_acoustics*>(base + sc.res);
@@ -233,7 +216,7 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     // 3. one walk for every band, then each band's finalize and analysis
     BandArgs ba;
     std::memset(&ba, 0, sizeof(ba));
-    ba.table = bs.d_table;
+    ba.table = bs.d_table.p;
     ba.hist = d_hist;
     ba.counters = d_cnt;
     ba.n_tris = bs.n_tris;
@@ -253,11 +236,11 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     if (acoustics)
         ARX_HIP(hipMemcpyAsync(h_res, d_res, (size_t)B * 3 * sizeof(arx_acoustics), hipMemcpyDeviceToHost, r->stream));
     // the tree as the probe's refit left it (a listener move): its off-grid flag, as arx_get_stats reads it
-    ARX_HIP(hipMemcpyAsync(r->h_tree_flag, r->d_tree_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipMemcpyAsync(r->h_tree_flag.p, r->d_tree_flag.p, sizeof(unsigned int), hipMemcpyDeviceToHost, r->stream));
     if (timed && (st = bs.timer.end(r->stream)) != ARX_OK) return st;
     // 4. the one synchronisation, then the host-side outputs
     ARX_HIP(hipStreamSynchronize(r->stream));
-    if (r->tree_gen != 0 && *r->h_tree_flag == r->tree_gen)
+    if (r->tree_gen != 0 && *r->h_tree_flag.p == r->tree_gen)
         return fail(ARX_ERR_INTERNAL, "receiver refit / re-quantization: a box left the quantization grid");
     bs.hist_bands = B;
     bs.hist_ir_len = r->ir_len;
@@ -280,12 +263,12 @@ int32_t arx_band_count(const arx_renderer* r) { return r ? r->bands.n_bands : 0;
 arx_status arx_debug_band_histograms(arx_renderer* r, int64_t* h_out, size_t capacity) {
     if (!r || !h_out) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
     const BandState& bs = r->bands;
-    if (bs.hist_bands < 1 || !bs.d_scratch) return fail(ARX_ERR_NOT_READY, "no arx_render_bands call has finished yet");
+    if (bs.hist_bands < 1 || !bs.d_scratch.p) return fail(ARX_ERR_NOT_READY, "no arx_render_bands call has finished yet");
     const size_t words = (size_t)bs.hist_bands * 2 * (size_t)bs.hist_ir_len;
     if (capacity < words) return fail(ARX_ERR_INVALID_ARGUMENT, "the histograms hold %zu words", words);
     ARX_HIP(hipSetDevice(r->cfg.device));
     // the last call ended synchronised; its histograms lead the scratch (band_scratch_layout)
-    ARX_HIP(hipMemcpy(h_out, static_cast<const char*>(bs.d_scratch) + band_scratch_layout(bs.hist_ir_len, bs.hist_bands).hist,
+    ARX_HIP(hipMemcpy(h_out, bs.d_scratch.p + band_scratch_layout(bs.hist_ir_len, bs.hist_bands).hist,
                       words * sizeof(int64_t), hipMemcpyDeviceToHost));
     return ARX_OK;
 }
@@ -358,18 +341,9 @@ arx_status arx_combine_bands(arx_renderer* r, const float* ir_left, const float*
     SynthScratch& sc = r->synth;
     ARX_HIP(hipSetDevice(r->cfg.device));
     if (const arx_status wt = fif_wait_conv(r); wt != ARX_OK) return wt;
-    if (lay.total > sc.bytes) {  // nothing of an earlier call is in flight: every call ends synchronised
-        hipFree(sc.d_scratch);
-        sc.d_scratch = nullptr;
-        sc.bytes = 0;
-        if (hipMalloc(&sc.d_scratch, lay.total) != hipSuccess) {
-            (void)hipGetLastError();
-            sc.d_scratch = nullptr;
-            return fail(ARX_ERR_OUT_OF_MEMORY, "the band combine's scratch of %llu bytes", (unsigned long long)lay.total);
-        }
-        sc.bytes = lay.total;
-    }
-    char* const base = static_cast<char*>(sc.d_scratch);
+    // nothing of an earlier call is in flight: every call ends synchronised
+    if (const arx_status rs = sc.d_scratch.reserve(lay.total); rs != ARX_OK) return rs;
+    char* const base = sc.d_scratch.p;
     const bool timed = r->timing || ms != nullptr;
     if (timed)
         if (const arx_status tb = sc.timer.begin(r->stream); tb != ARX_OK) return tb;

@@ -25,8 +25,8 @@ struct arx_stream {
     uint64_t ir_generation = ~0ull;  // the IR the partition spectra were made from
     int32_t fade_shape = ARX_FADE_HANN;  // arx_stream_set_crossfade (the frames: stream_plan_fade)
     uint64_t crossfades = 0;             // transition blocks processed
-    double* d_in = nullptr;          // host-API staging: block frames in, 2 * block out
-    double* d_out = nullptr;
+    DeviceBuf<double> d_in;          // host-API staging: block frames in, 2 * block out
+    DeviceBuf<double> d_out;
 };
 
 namespace {
@@ -46,7 +46,7 @@ arx_status ensure_conv(arx_renderer* r, bool spectra = true) {
         r->conv_ir_dirty = true;
     }
     if (spectra && r->conv_ir_dirty) {
-        ARX_HIP(conv_set_ir(r->conv, r->cur().d_ir, r->cur().d_ir + r->ir_len, r->stream));
+        ARX_HIP(conv_set_ir(r->conv, r->cur().d_ir.p, r->cur().d_ir.p + r->ir_len, r->stream));
         r->conv_ir_dirty = false;
     }
     return ARX_OK;
@@ -63,7 +63,7 @@ arx_status ensure_conv_live(arx_renderer* r, int32_t block) {
         r->conv_live_ir_dirty = true;
     }
     if (r->conv_live_ir_dirty) {
-        ARX_HIP(conv_set_ir(r->conv_live, r->cur().d_ir, r->cur().d_ir + r->ir_len, r->stream));
+        ARX_HIP(conv_set_ir(r->conv_live, r->cur().d_ir.p, r->cur().d_ir.p + r->ir_len, r->stream));
         r->conv_live_ir_dirty = false;
     }
     return ARX_OK;
@@ -74,11 +74,18 @@ void arx::release_stream(arx_stream* s) {
     hipSetDevice(s->device);
     if (s->r) sync_renderer(s->r);
     if (s->plan) stream_plan_destroy(s->plan);
-    hipFree(s->d_in);
-    hipFree(s->d_out);
+    s->d_in.release();
+    s->d_out.release();
     s->plan = nullptr;
-    s->d_in = s->d_out = nullptr;
     s->r = nullptr;
+}
+
+arx_status arx::reserve_conv_staging(arx_renderer* r, size_t n) {
+    if (n <= r->d_conv_in.cap && 2 * n <= r->d_conv_out.cap) return ARX_OK;
+    r->d_conv_in.release();
+    r->d_conv_out.release();
+    if (const arx_status st = r->d_conv_in.reserve(n); st != ARX_OK) return st;
+    return r->d_conv_out.reserve(2 * n);
 }
 
 arx_status arx::convolute_pairs(arx_renderer* r, const float* d_in, size_t n_frames, float* d_out_left,
@@ -91,7 +98,7 @@ arx_status arx::convolute_pairs(arx_renderer* r, const float* d_in, size_t n_fra
     if (st == ARX_OK) st = ensure_conv(r, false);
     if (st != ARX_OK) return st;
     const bool ir_new = r->conv_ir_dirty;
-    float* d_ir = r->cur().d_ir;
+    float* d_ir = r->cur().d_ir.p;
     if (timed && (st = r->conv_ring.begin(r->stream)) != ARX_OK) return st;
     ARX_HIP(conv_run_pairs(r->conv, d_in, (int64_t)n_frames, d_out_left, d_out_right, ir_new ? d_ir : nullptr,
                            ir_new ? d_ir + r->ir_len : nullptr, pair_begin, pair_end, r->stream));
@@ -110,7 +117,7 @@ arx_status arx_set_ir(arx_renderer* r, const float* h_left, const float* h_right
     if (!r || !h_left || !h_right) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
     if (ir_len != (size_t)r->ir_len) return fail(ARX_ERR_INVALID_ARGUMENT, "ir_len %zu != %d", ir_len, r->ir_len);
     ARX_HIP(hipSetDevice(r->cfg.device));
-    float* d_ir = r->cur().d_ir;
+    float* d_ir = r->cur().d_ir.p;
     ARX_HIP(hipMemcpyAsync(d_ir, h_left, ir_len * sizeof(float), hipMemcpyHostToDevice, r->stream));
     ARX_HIP(hipMemcpyAsync(d_ir + r->ir_len, h_right, ir_len * sizeof(float), hipMemcpyHostToDevice, r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));
@@ -124,7 +131,7 @@ arx_status arx_set_ir_device(arx_renderer* r, const float* d_left, const float* 
     if (!r || !d_left || !d_right) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
     if (ir_len != (size_t)r->ir_len) return fail(ARX_ERR_INVALID_ARGUMENT, "ir_len %zu != %d", ir_len, r->ir_len);
     ARX_HIP(hipSetDevice(r->cfg.device));
-    float* d_ir = r->cur().d_ir;
+    float* d_ir = r->cur().d_ir.p;
     ARX_HIP(hipMemcpyAsync(d_ir, d_left, ir_len * sizeof(float), hipMemcpyDeviceToDevice, r->stream));
     ARX_HIP(hipMemcpyAsync(d_ir + r->ir_len, d_right, ir_len * sizeof(float), hipMemcpyDeviceToDevice, r->stream));
     r->conv_ir_dirty = true;
@@ -181,7 +188,7 @@ arx_status arx_convolute_prepared(arx_renderer* r, float* d_out_left, float* d_o
     arx_status st = fif_wait_conv(r);
     if (st != ARX_OK) return st;
     const bool ir_new = r->conv_ir_dirty;
-    float* d_ir = r->cur().d_ir;
+    float* d_ir = r->cur().d_ir.p;
     if (r->timing && (st = r->conv_ring.begin(r->stream)) != ARX_OK) return st;
     ARX_HIP(conv_run_prepared(r->conv, d_out_left, d_out_right, ir_new ? d_ir : nullptr, ir_new ? d_ir + r->ir_len : nullptr,
                               r->stream));
@@ -209,23 +216,15 @@ arx_status arx_convolute_audio_file(arx_renderer* r, const float* h_in, size_t i
     ARX_HIP(hipEventCreate(&ev.e[1]));
     hipEvent_t p0 = ev.e[0], p1 = ev.e[1];
     ARX_HIP(hipEventRecord(p0, r->stream));
-    if (n > r->conv_cap) {
-        hipFree(r->d_conv_in);
-        hipFree(r->d_conv_out);
-        r->d_conv_in = r->d_conv_out = nullptr;
-        r->conv_cap = 0;
-        ARX_HIP(hipMalloc(&r->d_conv_in, n * sizeof(float)));
-        ARX_HIP(hipMalloc(&r->d_conv_out, 2 * n * sizeof(float)));
-        r->conv_cap = n;
-    }
-    if (n > 0) ARX_HIP(hipMemcpyAsync(r->d_conv_in, h_in, n * sizeof(float), hipMemcpyHostToDevice, r->stream));
+    if (const arx_status rs = reserve_conv_staging(r, n); rs != ARX_OK) return rs;
+    if (n > 0) ARX_HIP(hipMemcpyAsync(r->d_conv_in.p, h_in, n * sizeof(float), hipMemcpyHostToDevice, r->stream));
     // timed when asked for the convolution's own window
-    const arx_status st = convolute_pairs(r, r->d_conv_in, n, r->d_conv_out, r->d_conv_out + n, 0, INT64_MAX,
+    const arx_status st = convolute_pairs(r, r->d_conv_in.p, n, r->d_conv_out.p, r->d_conv_out.p + n, 0, INT64_MAX,
                                           r->timing || conv_ms != nullptr);
     if (st != ARX_OK) return st;
     if (n > 0) {
-        ARX_HIP(hipMemcpyAsync(h_out_left, r->d_conv_out, n * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-        ARX_HIP(hipMemcpyAsync(h_out_right, r->d_conv_out + n, n * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+        ARX_HIP(hipMemcpyAsync(h_out_left, r->d_conv_out.p, n * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+        ARX_HIP(hipMemcpyAsync(h_out_right, r->d_conv_out.p + n, n * sizeof(float), hipMemcpyDeviceToHost, r->stream));
     }
     ARX_HIP(hipEventRecord(p1, r->stream));
     ARX_HIP(hipEventSynchronize(p1));
@@ -265,14 +264,12 @@ arx_status arx_convolute_live_block(arx_renderer* r, const double* h_in, size_t 
         return fail(ARX_ERR_INVALID_ARGUMENT, "live block of %zu samples exceeds ir_len %d", n_in, r->ir_len);
     ARX_HIP(hipSetDevice(r->cfg.device));
     if (const arx_status w = fif_wait_conv(r); w != ARX_OK) return w;  // the staging buffers below
-    if (!r->d_live_in) {
-        ARX_HIP(hipMalloc(&r->d_live_in, (size_t)r->ir_len * sizeof(double)));
-        ARX_HIP(hipMalloc(&r->d_live_out, 2 * (size_t)r->ir_len * sizeof(double)));
-    }
-    if (n_in > 0) ARX_HIP(hipMemcpyAsync(r->d_live_in, h_in, n_in * sizeof(double), hipMemcpyHostToDevice, r->stream));
-    arx_status st = arx_convolute_live_device(r, r->d_live_in, n_in, r->d_live_out);
-    if (st != ARX_OK) return st;
-    ARX_HIP(hipMemcpyAsync(h_out, r->d_live_out, out_len * sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    arx_status st;
+    if ((st = r->d_live_in.reserve((size_t)r->ir_len)) != ARX_OK || (st = r->d_live_out.reserve(2 * (size_t)r->ir_len)) != ARX_OK)
+        return st;
+    if (n_in > 0) ARX_HIP(hipMemcpyAsync(r->d_live_in.p, h_in, n_in * sizeof(double), hipMemcpyHostToDevice, r->stream));
+    if ((st = arx_convolute_live_device(r, r->d_live_in.p, n_in, r->d_live_out.p)) != ARX_OK) return st;
+    ARX_HIP(hipMemcpyAsync(h_out, r->d_live_out.p, out_len * sizeof(double), hipMemcpyDeviceToHost, r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));
     return ARX_OK;
 }
@@ -295,11 +292,11 @@ arx_status arx_stream_create(arx_renderer* r, int32_t block_frames, arx_stream**
         delete s;
         return fail(ARX_ERR_INTERNAL, "stream plan: %s", err);
     }
-    if (hipMalloc(&s->d_in, (size_t)block_frames * sizeof(double)) != hipSuccess ||
-        hipMalloc(&s->d_out, 2 * (size_t)block_frames * sizeof(double)) != hipSuccess) {
+    arx_status st;
+    if ((st = s->d_in.reserve((size_t)block_frames)) != ARX_OK || (st = s->d_out.reserve(2 * (size_t)block_frames)) != ARX_OK) {
         release_stream(s);
         delete s;
-        return fail(ARX_ERR_OUT_OF_MEMORY, "stream buffers");
+        return st;
     }
     r->streams.push_back(s);
     *out = s;
@@ -347,7 +344,7 @@ arx_status arx_stream_process_device(arx_stream* s, const double* d_in, size_t n
         // a transition block: a fade is on and the last block (since creation or the last reset) ran
         // with the spectra that are current until now; they become the previous set
         transition = stream_plan_fade(s->plan) > 0 && s->ir_generation != ~0ull && stream_plan_blocks(s->plan) > 0;
-        ARX_HIP(stream_set_ir(s->plan, r->cur().d_ir, r->cur().d_ir + r->ir_len, transition, r->stream));
+        ARX_HIP(stream_set_ir(s->plan, r->cur().d_ir.p, r->cur().d_ir.p + r->ir_len, transition, r->stream));
         s->ir_generation = r->ir_generation;
     }
     if (const arx_status t = r->live_ring.begin(r->stream); t != ARX_OK) return t;
@@ -419,10 +416,10 @@ arx_status arx_stream_process(arx_stream* s, const double* h_in, size_t n_frames
     ARX_HIP(hipSetDevice(r->cfg.device));
     if (const arx_status w = fif_wait_conv(r); w != ARX_OK) return w;  // the staging buffers below
     if (n_frames > 0)
-        ARX_HIP(hipMemcpyAsync(s->d_in, h_in, n_frames * sizeof(double), hipMemcpyHostToDevice, r->stream));
-    const arx_status st = arx_stream_process_device(s, s->d_in, n_frames, s->d_out);
+        ARX_HIP(hipMemcpyAsync(s->d_in.p, h_in, n_frames * sizeof(double), hipMemcpyHostToDevice, r->stream));
+    const arx_status st = arx_stream_process_device(s, s->d_in.p, n_frames, s->d_out.p);
     if (st != ARX_OK) return st;
-    ARX_HIP(hipMemcpyAsync(h_out, s->d_out, out_len * sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipMemcpyAsync(h_out, s->d_out.p, out_len * sizeof(double), hipMemcpyDeviceToHost, r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));
     return ARX_OK;
 }
@@ -490,19 +487,11 @@ arx_status arx_convolute_walk(arx_renderer* r, const float* ir_left, const float
 
     ARX_HIP(hipSetDevice(r->cfg.device));
     if (const arx_status wt = fif_wait_conv(r); wt != ARX_OK) return wt;
-    if (lay.total > w.bytes) {  // nothing of an earlier call is in flight: every call ends synchronised
-        hipFree(w.d_scratch);
-        w.d_scratch = nullptr;
-        w.bytes = 0;
+    if (lay.total > w.d_scratch.cap) {  // nothing of an earlier call is in flight: every call ends synchronised
         w.tw_n = 0;
-        if (hipMalloc(&w.d_scratch, lay.total) != hipSuccess) {
-            (void)hipGetLastError();
-            w.d_scratch = nullptr;
-            return fail(ARX_ERR_OUT_OF_MEMORY, "the walk's scratch of %llu bytes", (unsigned long long)lay.total);
-        }
-        w.bytes = lay.total;
+        if (const arx_status rs = w.d_scratch.reserve(lay.total); rs != ARX_OK) return rs;
     }
-    char* base = static_cast<char*>(w.d_scratch);
+    char* base = w.d_scratch.p;
     const bool timed = r->timing || ms != nullptr;
     if (timed)
         if (const arx_status tb = w.timer.begin(r->stream); tb != ARX_OK) return tb;
@@ -530,7 +519,7 @@ arx_status arx_convolute_walk(arx_renderer* r, const float* ir_left, const float
     }
     if (n_frames > 0) ARX_HIP(hipMemcpyAsync(base + lay.in, in, n_frames * sizeof(double), hipMemcpyDefault, r->stream));
     WalkArgs a{};
-    a.scratch = w.d_scratch;
+    a.scratch = w.d_scratch.p;
     a.layout = lay;
     a.ir_len = r->ir_len;
     a.n_frames = (int64_t)n_frames;
@@ -597,11 +586,3 @@ arx_status arx_debug_walk_state(arx_renderer* r, uint64_t out5[5]) {
 }
 
 }  // extern "C"
-
-void arx::free_walk(WalkScratch& w) {
-    hipFree(w.d_scratch);
-    w.timer.destroy();
-    const int32_t forced = w.forced_tile;
-    w = WalkScratch{};
-    w.forced_tile = forced;
-}

@@ -111,24 +111,24 @@ arx_status prepare_receiver_model(arx_renderer* r) {
         r->recv_refit = false;  // beyond one workgroup's LDS: rebuilt on the host per move instead
         return ARX_OK;
     }
-    hipFree(r->d_recv_local);
-    hipFree(r->d_recv_nodes);
-    hipFree(r->d_recv_levels);
-    r->d_recv_local = nullptr;
-    r->d_recv_nodes = nullptr;
-    r->d_recv_levels = nullptr;
-    ARX_HIP(hipMalloc(&r->d_recv_local, std::max<size_t>(1, r->recv.tris.size()) * sizeof(TriRec)));
-    ARX_HIP(hipMalloc(&r->d_recv_nodes, std::max<size_t>(1, r->recv.nodes.size()) * sizeof(BvhNode)));
-    ARX_HIP(hipMalloc(&r->d_recv_levels, (order.size() + start.size()) * sizeof(int32_t)));
+    // made anew for every model, at its size
+    arx_status st;
+    r->d_recv_local.release();
+    r->d_recv_nodes.release();
+    r->d_recv_levels.release();
+    if ((st = r->d_recv_local.reserve(std::max<size_t>(1, r->recv.tris.size()))) != ARX_OK ||
+        (st = r->d_recv_nodes.reserve(std::max<size_t>(1, r->recv.nodes.size()))) != ARX_OK ||
+        (st = r->d_recv_levels.reserve(order.size() + start.size())) != ARX_OK)
+        return st;
     if (!r->recv.tris.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_recv_local, r->recv.tris.data(), r->recv.tris.size() * sizeof(TriRec),
+        ARX_HIP(hipMemcpyAsync(r->d_recv_local.p, r->recv.tris.data(), r->recv.tris.size() * sizeof(TriRec),
                                hipMemcpyHostToDevice, r->stream));
     if (!r->recv.nodes.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_recv_nodes, r->recv.nodes.data(), r->recv.nodes.size() * sizeof(BvhNode),
+        ARX_HIP(hipMemcpyAsync(r->d_recv_nodes.p, r->recv.nodes.data(), r->recv.nodes.size() * sizeof(BvhNode),
                                hipMemcpyHostToDevice, r->stream));
     std::vector<int32_t> lv(order);
     lv.insert(lv.end(), start.begin(), start.end());
-    ARX_HIP(hipMemcpyAsync(r->d_recv_levels, lv.data(), lv.size() * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
+    ARX_HIP(hipMemcpyAsync(r->d_recv_levels.p, lv.data(), lv.size() * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));  // pageable sources
     r->recv_level_count = (int32_t)order.size();
     if (!r->use_w4) return ARX_OK;
@@ -147,16 +147,15 @@ arx_status prepare_receiver_model(arx_renderer* r) {
         w4t[2 * i] = (int32_t)r->recv4.leaf_tris[i].first;
         w4t[2 * i + 1] = r->recv4.leaf_tris[i].second;
     }
-    hipFree(r->d_recv_w4);
-    hipFree(r->d_recv_w4_tris);
-    r->d_recv_w4 = nullptr;
-    r->d_recv_w4_tris = nullptr;
-    ARX_HIP(hipMalloc(&r->d_recv_w4, std::max<size_t>(1, w4n.size()) * sizeof(int32_t)));
-    ARX_HIP(hipMalloc(&r->d_recv_w4_tris, std::max<size_t>(1, w4t.size()) * sizeof(int32_t)));
+    r->d_recv_w4.release();
+    r->d_recv_w4_tris.release();
+    if ((st = r->d_recv_w4.reserve(std::max<size_t>(1, w4n.size()))) != ARX_OK ||
+        (st = r->d_recv_w4_tris.reserve(std::max<size_t>(1, w4t.size()))) != ARX_OK)
+        return st;
     if (!w4n.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_recv_w4, w4n.data(), w4n.size() * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
+        ARX_HIP(hipMemcpyAsync(r->d_recv_w4.p, w4n.data(), w4n.size() * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
     if (!w4t.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_recv_w4_tris, w4t.data(), w4t.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+        ARX_HIP(hipMemcpyAsync(r->d_recv_w4_tris.p, w4t.data(), w4t.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                                r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));  // pageable sources
     return ARX_OK;
@@ -235,25 +234,25 @@ void place_host_receiver(arx_renderer* r) {
 // (host-built receivers) the receiver's).  An array that is re-made holds nothing: u.full.
 arx_status reserve_tree(arx_renderer* r, SceneUpdate& u) {
     arx_status st;
-    if (u.n_nodes > r->nodes_cap) {
-        if ((st = grow_device(&r->d_cnodes, &r->nodes_cap, u.n_nodes, 1024, sizeof(BvhNode))) != ARX_OK) return st;
-        if ((st = grow_device(&r->d_qnodes, &r->nodes_cap, u.n_nodes, 1024, sizeof(QNode2))) != ARX_OK) return st;
+    if (u.n_nodes > r->nodes_cap()) {
+        if ((st = r->d_cnodes.reserve(u.n_nodes, 1024)) != ARX_OK || (st = r->d_qnodes.reserve(u.n_nodes, 1024)) != ARX_OK)
+            return st;
         u.full = true;
     }
-    if (u.n_tris > r->tris_cap || r->d_tris == nullptr) {
-        if ((st = grow_device(&r->d_tris, &r->tris_cap, u.n_tris, 4096, sizeof(TriRec))) != ARX_OK) return st;
+    if (u.n_tris > r->d_tris.cap || !r->d_tris.p) {
+        if ((st = r->d_tris.reserve(u.n_tris, 4096)) != ARX_OK) return st;
         u.full = true;
     }
     const SceneImage::Wide& wide = wide_of(r);
     const size_t w_units = r->use_w4 ? std::max<size_t>(r->recv4.unit_end, wide.w4.unit_end) : 0;
     const size_t host_recv_w4 = (r->recv_refit || !r->use_w4) ? 0 : r->recv4.nodes.size();
     const size_t n_w4f = r->use_w4 ? 1 + wide.w4.nodes.size() + host_recv_w4 : 0;
-    if (w_units > r->wbuf_cap) {
-        if ((st = grow_device(&r->d_wbuf, &r->wbuf_cap, w_units, 4096, 16)) != ARX_OK) return st;
+    if (w_units > r->d_wbuf.cap) {
+        if ((st = r->d_wbuf.reserve(w_units, 4096)) != ARX_OK) return st;
         u.full = true;
     }
-    if (n_w4f > r->w4f_cap) {
-        if ((st = grow_device(&r->d_w4f, &r->w4f_cap, n_w4f, 1024, sizeof(W4NodeF))) != ARX_OK) return st;
+    if (n_w4f > r->d_w4f.cap) {
+        if ((st = r->d_w4f.reserve(n_w4f, 1024)) != ARX_OK) return st;
         u.full = true;
     }
     r->n_w4f = n_w4f;
@@ -301,23 +300,23 @@ arx_status upload_w4(arx_renderer* r, bool full, W4NodeF& wtop, std::vector<uint
             wtop.hi[1][k] = r->recv.root.hi[k];
         }
     }
-    ARX_HIP(hipMemcpyAsync(r->d_w4f, &wtop, sizeof(W4NodeF), hipMemcpyHostToDevice, r->stream));
+    ARX_HIP(hipMemcpyAsync(r->d_w4f.p, &wtop, sizeof(W4NodeF), hipMemcpyHostToDevice, r->stream));
     if (full && !wide.wimage.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_wbuf, wide.wimage.data(), wide.wimage.size() * sizeof(uint32_t),
+        ARX_HIP(hipMemcpyAsync(r->d_wbuf.p, wide.wimage.data(), wide.wimage.size() * sizeof(uint32_t),
                                hipMemcpyHostToDevice, r->stream));
     if (full && !wide.w4.nodes.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_w4f + 1, wide.w4.nodes.data(), wide.w4.nodes.size() * sizeof(W4NodeF),
+        ARX_HIP(hipMemcpyAsync(r->d_w4f.p + 1, wide.w4.nodes.data(), wide.w4.nodes.size() * sizeof(W4NodeF),
                                hipMemcpyHostToDevice, r->stream));
     if (!host_recv) return ARX_OK;
     if (!r->recv4.nodes.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_w4f + 1 + wide.w4.nodes.size(), r->recv4.nodes.data(),
+        ARX_HIP(hipMemcpyAsync(r->d_w4f.p + 1 + wide.w4.nodes.size(), r->recv4.nodes.data(),
                                r->recv4.nodes.size() * sizeof(W4NodeF), hipMemcpyHostToDevice, r->stream));
     const size_t u0 = wide.w4.unit_end;
     rimage.assign((r->recv4.unit_end - u0) * 4, 0u);
     for (const auto& lt : r->recv4.leaf_tris)
         std::memcpy(rimage.data() + (size_t)(lt.first - u0) * 4, &r->recv.tris[(size_t)lt.second], sizeof(TriRec));
     if (!rimage.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_wbuf + u0, rimage.data(), rimage.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+        ARX_HIP(hipMemcpyAsync(r->d_wbuf.p + u0, rimage.data(), rimage.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                r->stream));
     return ARX_OK;
 }
@@ -339,18 +338,18 @@ arx_status upload_tree(arx_renderer* r, const SceneUpdate& u) {
     code_nodes(&top, 1, &ctop);
     std::vector<BvhNode> crecv(host_recv ? r->recv.nodes.size() : 0);
     if (host_recv) code_nodes(r->recv.nodes.data(), r->recv.nodes.size(), crecv.data());
-    ARX_HIP(hipMemcpyAsync(r->d_cnodes, &ctop, sizeof(BvhNode), hipMemcpyHostToDevice, r->stream));
+    ARX_HIP(hipMemcpyAsync(r->d_cnodes.p, &ctop, sizeof(BvhNode), hipMemcpyHostToDevice, r->stream));
     if (u.full && !img.coded.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_cnodes + 1, img.coded.data(), img.coded.size() * sizeof(BvhNode),
+        ARX_HIP(hipMemcpyAsync(r->d_cnodes.p + 1, img.coded.data(), img.coded.size() * sizeof(BvhNode),
                                hipMemcpyHostToDevice, r->stream));
     if (u.full && !sc.tris.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_tris, sc.tris.data(), sc.tris.size() * sizeof(TriRec), hipMemcpyHostToDevice,
+        ARX_HIP(hipMemcpyAsync(r->d_tris.p, sc.tris.data(), sc.tris.size() * sizeof(TriRec), hipMemcpyHostToDevice,
                                r->stream));
     if (host_recv && !crecv.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_cnodes + 1 + sc.nodes.size(), crecv.data(), crecv.size() * sizeof(BvhNode),
+        ARX_HIP(hipMemcpyAsync(r->d_cnodes.p + 1 + sc.nodes.size(), crecv.data(), crecv.size() * sizeof(BvhNode),
                                hipMemcpyHostToDevice, r->stream));
     if (host_recv && !r->recv.tris.empty())
-        ARX_HIP(hipMemcpyAsync(r->d_tris + sc.tris.size(), r->recv.tris.data(), r->recv.tris.size() * sizeof(TriRec),
+        ARX_HIP(hipMemcpyAsync(r->d_tris.p + sc.tris.size(), r->recv.tris.data(), r->recv.tris.size() * sizeof(TriRec),
                                hipMemcpyHostToDevice, r->stream));
     W4NodeF wtop;
     std::vector<uint32_t> rimage;
@@ -370,10 +369,10 @@ arx_status refit_receiver(arx_renderer* r) {
     a.pad = refit_pad(r, r->center);
     if (!r->q_valid) a.qnodes = nullptr;
     if (r->q_valid && r->use_w4) {  // the opt-in CW4 copy follows the quantized one (same grid)
-        a.wbuf = r->d_wbuf;
-        a.w4_nodes = r->d_recv_w4;
+        a.wbuf = r->d_wbuf.p;
+        a.w4_nodes = r->d_recv_w4.p;
         a.n_w4 = (int32_t)r->recv4.nodes.size();
-        a.w4_tris = r->d_recv_w4_tris;
+        a.w4_tris = r->d_recv_w4_tris.p;
         a.n_w4_tris = (int32_t)r->recv4.leaf_tris.size();
         a.scene_nonempty = sc.root.count >= 0 ? 1 : 0;
         for (int k = 0; k < 3; ++k) {
@@ -418,22 +417,22 @@ RefitArgs arx::refit_args(const arx_renderer* r) {
     const BvhBuild& sc = r->scene_img->bvh;
     RefitArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.local_tris = r->d_recv_local;
+    a.local_tris = r->d_recv_local.p;
     a.n_tris = (int32_t)r->recv.tris.size();
     a.tri_base = (int32_t)sc.tris.size();
-    a.local_nodes = r->d_recv_nodes;
+    a.local_nodes = r->d_recv_nodes.p;
     a.n_nodes = (int32_t)r->recv.nodes.size();
     a.node_base = 1 + (int32_t)sc.nodes.size();
-    a.level_nodes = r->d_recv_levels;
-    a.level_start = r->d_recv_levels + r->recv_level_count;
+    a.level_nodes = r->d_recv_levels.p;
+    a.level_start = r->d_recv_levels.p + r->recv_level_count;
     a.n_levels = r->recv_levels;
     a.root_ref = r->recv.root.ref;
     a.root_count = r->recv.root.count;
     a.grid = r->qgrid;
-    a.tris = r->d_tris;
-    a.cnodes = r->d_cnodes;
-    a.qnodes = r->d_qnodes;
-    a.flag = r->d_tree_flag;
+    a.tris = r->d_tris.p;
+    a.cnodes = r->d_cnodes.p;
+    a.qnodes = r->d_qnodes.p;
+    a.flag = r->d_tree_flag.p;
     a.flag_value = r->tree_gen;
     return a;
 }
@@ -469,9 +468,9 @@ arx_status arx::ensure_device_scene(arx_renderer* r) {
         // coded nodes on the device; on the refit path the refit below writes the receiver's
         // quantized nodes itself (its coded ones may not exist yet)
         const size_t nq = host_recv ? u.n_nodes : 1 + sc.nodes.size();
-        ARX_HIP(launch_requant16(r->d_cnodes, nq, r->qgrid, r->d_qnodes, r->d_tree_flag, r->tree_gen, r->stream));
+        ARX_HIP(launch_requant16(r->d_cnodes.p, nq, r->qgrid, r->d_qnodes.p, r->d_tree_flag.p, r->tree_gen, r->stream));
         if (r->use_w4)
-            ARX_HIP(launch_requant_w4(r->d_w4f, r->n_w4f, r->qgrid, r->d_wbuf, r->d_tree_flag, r->tree_gen, r->stream));
+            ARX_HIP(launch_requant_w4(r->d_w4f.p, r->n_w4f, r->qgrid, r->d_wbuf.p, r->d_tree_flag.p, r->tree_gen, r->stream));
         ++r->requants;
     }
     r->q_valid = u.recv_empty || qgrid_contains(r->qgrid, u.rlo, u.rhi);
@@ -493,45 +492,40 @@ arx_status arx::grow_grid_for(arx_renderer* r, const float ulo[3], const float u
     const BvhBuild& sc = r->scene_img->bvh;
     ++r->tree_gen;
     r->qgrid = span_grid(r, ulo, uhi, true);
-    ARX_HIP(launch_requant16(r->d_cnodes, 1 + sc.nodes.size(), r->qgrid, r->d_qnodes, r->d_tree_flag, r->tree_gen, r->stream));
+    ARX_HIP(launch_requant16(r->d_cnodes.p, 1 + sc.nodes.size(), r->qgrid, r->d_qnodes.p, r->d_tree_flag.p, r->tree_gen, r->stream));
     ++r->requants;
     r->recv_pose_dirty = true;
     return ARX_OK;
 }
 
 bool arx::widen_tree_arrays(arx_renderer* r, size_t need_nodes, size_t need_tris) {
-    if (need_nodes <= r->nodes_cap && need_tris <= r->tris_cap) return true;
+    if (need_nodes <= r->nodes_cap() && need_tris <= r->d_tris.cap) return true;
     if (sync_renderer(r) != ARX_OK) return false;
-    if (need_nodes > r->nodes_cap) {
+    if (need_nodes > r->nodes_cap()) {
         BvhNode* cn = nullptr;
         QNode2* qn = nullptr;
         const size_t cap = need_nodes + 1024;
         if (hipMalloc(&cn, cap * sizeof(BvhNode)) != hipSuccess || hipMalloc(&qn, cap * sizeof(QNode2)) != hipSuccess ||
-            hipMemcpy(cn, r->d_cnodes, r->nodes_cap * sizeof(BvhNode), hipMemcpyDeviceToDevice) != hipSuccess ||
-            hipMemcpy(qn, r->d_qnodes, r->nodes_cap * sizeof(QNode2), hipMemcpyDeviceToDevice) != hipSuccess) {
+            hipMemcpy(cn, r->d_cnodes.p, r->d_cnodes.bytes(), hipMemcpyDeviceToDevice) != hipSuccess ||
+            hipMemcpy(qn, r->d_qnodes.p, r->d_qnodes.bytes(), hipMemcpyDeviceToDevice) != hipSuccess) {
             (void)hipGetLastError();
             hipFree(cn);
             hipFree(qn);
             return false;
         }
-        hipFree(r->d_cnodes);
-        hipFree(r->d_qnodes);
-        r->d_cnodes = cn;
-        r->d_qnodes = qn;
-        r->nodes_cap = cap;
+        r->d_cnodes.adopt(cn, cap);
+        r->d_qnodes.adopt(qn, cap);
     }
-    if (need_tris > r->tris_cap) {
+    if (need_tris > r->d_tris.cap) {
         TriRec* tr = nullptr;
         const size_t cap = need_tris + 4096;
         if (hipMalloc(&tr, cap * sizeof(TriRec)) != hipSuccess ||
-            hipMemcpy(tr, r->d_tris, r->tris_cap * sizeof(TriRec), hipMemcpyDeviceToDevice) != hipSuccess) {
+            hipMemcpy(tr, r->d_tris.p, r->d_tris.bytes(), hipMemcpyDeviceToDevice) != hipSuccess) {
             (void)hipGetLastError();
             hipFree(tr);
             return false;
         }
-        hipFree(r->d_tris);
-        r->d_tris = tr;
-        r->tris_cap = cap;
+        r->d_tris.adopt(tr, cap);
     }
     return true;
 }
@@ -584,8 +578,8 @@ arx_status arx_debug_node_images(arx_renderer* r, void* cnodes, void* qnodes, si
     if (n_nodes > (size_t)r->stats.n_nodes) return fail(ARX_ERR_INVALID_ARGUMENT, "only %lld nodes", (long long)r->stats.n_nodes);
     ARX_HIP(hipSetDevice(r->cfg.device));
     ARX_HIP(hipStreamSynchronize(r->stream));
-    if (cnodes && n_nodes) ARX_HIP(hipMemcpy(cnodes, r->d_cnodes, n_nodes * sizeof(BvhNode), hipMemcpyDeviceToHost));
-    if (qnodes && n_nodes) ARX_HIP(hipMemcpy(qnodes, r->d_qnodes, n_nodes * sizeof(QNode2), hipMemcpyDeviceToHost));
+    if (cnodes && n_nodes) ARX_HIP(hipMemcpy(cnodes, r->d_cnodes.p, n_nodes * sizeof(BvhNode), hipMemcpyDeviceToHost));
+    if (qnodes && n_nodes) ARX_HIP(hipMemcpy(qnodes, r->d_qnodes.p, n_nodes * sizeof(QNode2), hipMemcpyDeviceToHost));
     if (grid)
         for (int k = 0; k < 3; ++k) {
             grid[k] = r->qgrid.origin[k];

@@ -54,12 +54,6 @@ arx_status check_orientation(const float* m) {
 
 }  // namespace
 
-void arx::free_directivity(DirectivityState& d) {
-    hipFree(d.d_cube);
-    hipFree(d.d_plane);
-    d = DirectivityState{};
-}
-
 arx_status arx::directivity_check_bands(const arx_renderer* r, int32_t n_bands) {
     const int32_t p = r->directivity.n_bands;
     if (p > 1 && p != n_bands)
@@ -74,10 +68,10 @@ arx_status arx::directivity_plane(arx_renderer* r, const void* dirs, uint64_t n,
     if (const arx_status st = directivity_check_bands(r, n_bands); st != ARX_OK) return st;
     if (!dirs || n < 1 || n_bands < 1 || n_bands > kMaxBands) return fail(ARX_ERR_INTERNAL, "directivity plane: no recording");
     const uint64_t rec = r->path_cache.rec_gen;
-    const uint64_t need = n * (uint64_t)band_width(n_bands) * sizeof(float);
-    if (need > d.plane_cap) {
+    const uint64_t need = n * (uint64_t)band_width(n_bands);  // floats
+    if (need > d.d_plane.cap) {
         d.plane_valid = false;
-        if (const arx_status st = grow_device(&d.d_plane, &d.plane_cap, need, 0, 1); st != ARX_OK) return st;
+        if (const arx_status st = d.d_plane.reserve(need); st != ARX_OK) return st;
     }
     if (!d.plane_valid || d.made_pattern != d.pattern_gen || d.made_orient != d.orient_gen || d.made_rec != rec ||
         d.made_rays != n || d.made_bands != n_bands) {
@@ -85,8 +79,8 @@ arx_status arx::directivity_plane(arx_renderer* r, const void* dirs, uint64_t n,
         GainArgs g;
         std::memset(&g, 0, sizeof(g));
         g.dirs = static_cast<const float*>(dirs);
-        g.cube = d.d_cube;
-        g.plane = d.d_plane;
+        g.cube = d.d_cube.p;
+        g.plane = d.d_plane.p;
         g.n = n;
         std::memcpy(g.m, d.m, sizeof(g.m));
         g.res = d.res;
@@ -101,7 +95,7 @@ arx_status arx::directivity_plane(arx_renderer* r, const void* dirs, uint64_t n,
         d.plane_valid = true;
         ++d.planes_made;
     }
-    *plane = d.d_plane;
+    *plane = d.d_plane.p;
     return ARX_OK;
 }
 
@@ -119,10 +113,10 @@ arx_status arx_set_source_directivity(arx_renderer* r, const float* cube, int32_
     ARX_HIP(hipSetDevice(r->cfg.device));
     d.n_bands = 0;  // a device error below drops the pattern
     ++d.pattern_gen;
-    const uint64_t need = cube_floats(n_bands, res) * sizeof(float);
-    if (need > d.cube_cap)  // no call is in flight: every band call ends synchronised
-        if (const arx_status st = grow_device(&d.d_cube, &d.cube_cap, need, 0, 1); st != ARX_OK) return st;
-    ARX_HIP(hipMemcpy(d.d_cube, cube, need, hipMemcpyHostToDevice));
+    const uint64_t need = cube_floats(n_bands, res);
+    // no call is in flight: every band call ends synchronised
+    if (const arx_status st = d.d_cube.reserve(need); st != ARX_OK) return st;
+    ARX_HIP(hipMemcpy(d.d_cube.p, cube, need * sizeof(float), hipMemcpyHostToDevice));
     d.n_bands = n_bands;
     d.res = res;
     return ARX_OK;
@@ -168,7 +162,7 @@ arx_status arx_debug_directivity_plane(arx_renderer* r, uint64_t first_ray, uint
     DirectivityState& d = r->directivity;
     const PathCache& pc = r->path_cache;
     if (d.n_bands < 1) return fail(ARX_ERR_NOT_READY, "arx_set_source_directivity has not been called");
-    if (!pc.recorded || !pc.d_dirs || pc.rec_rays == 0) return fail(ARX_ERR_NOT_READY, "the path cache holds no recording to make a plane from");
+    if (!pc.recorded || !pc.d_dirs.p || pc.rec_rays == 0) return fail(ARX_ERR_NOT_READY, "the path cache holds no recording to make a plane from");
     if (r->stream != r->cur().stream) return fail(ARX_ERR_INVALID_ARGUMENT, "the plane is made on the renderer's own stream");
     // the band count the next band call will run with: the table's, or without a table the pattern's
     const int32_t B = r->bands.n_bands >= 1 ? r->bands.n_bands : d.n_bands;
@@ -178,7 +172,7 @@ arx_status arx_debug_directivity_plane(arx_renderer* r, uint64_t first_ray, uint
     ARX_HIP(hipSetDevice(r->cfg.device));
     if (pc.rec_stream != r->stream) ARX_HIP(hipStreamWaitEvent(r->stream, pc.ev_recorded, 0));
     const float* plane = nullptr;
-    if (const arx_status st = directivity_plane(r, pc.d_dirs, pc.rec_rays, B, &plane); st != ARX_OK) return st;
+    if (const arx_status st = directivity_plane(r, pc.d_dirs.p, pc.rec_rays, B, &plane); st != ARX_OK) return st;
     const uint64_t W = (uint64_t)band_width(B);
     if (count > 0)
         ARX_HIP(hipMemcpyAsync(h_out, plane + first_ray * W, count * W * sizeof(float), hipMemcpyDeviceToHost, r->stream));

@@ -57,13 +57,13 @@ arx_status warm_up(ListenerCall& c) { return record_for_bands(c.r, c.N, &c.poses
 BandArgs band_args(const ListenerCall& c) {
     BandArgs ba;
     std::memset(&ba, 0, sizeof(ba));
-    ba.table = c.r->bands.d_table;
+    ba.table = c.r->bands.d_table.p;
     ba.counters = c.at<unsigned long long>(c.sc.base);
     ba.n_tris = c.r->bands.n_tris;
     ba.n_bands = c.bands;
     // a source pattern: the plane begin_chunks made for this call's recording
     const DirectivityState& d = c.r->directivity;
-    ba.gain = d.n_bands >= 1 && d.plane_valid ? d.d_plane : nullptr;
+    ba.gain = d.n_bands >= 1 && d.plane_valid ? d.d_plane.p : nullptr;
     return ba;
 }
 
@@ -73,7 +73,7 @@ arx_status begin_chunks(ListenerCall& lc) {
     BandCall& c = static_cast<BandCall&>(lc);
     arx_renderer* r = c.r;
     if (c.filters)
-        ARX_HIP(hipMemcpyAsync(c.own->d_filters, c.filters, (size_t)c.bands * (size_t)c.taps * sizeof(double), hipMemcpyDefault,
+        ARX_HIP(hipMemcpyAsync(c.own->d_filters.p, c.filters, (size_t)c.bands * (size_t)c.taps * sizeof(double), hipMemcpyDefault,
                                r->stream));
     const float* plane = nullptr;  // the gain plane of a source pattern, remade only when stale (band_args reads it)
     if (const arx_status st = directivity_plane(r, c.probe.args.dirs, c.N, c.bands, &plane); st != ARX_OK) return st;
@@ -95,7 +95,7 @@ arx_status combine(ListenerCall& lc, int32_t i, size_t j) {
     BandSynthArgs a{};
     a.ir_left = c.at<float>(c.sc.ir) + (size_t)i * set;
     a.ir_right = a.ir_left + (size_t)c.chunk * set;
-    a.filters = static_cast<const double*>(c.own->d_filters);
+    a.filters = c.own->d_filters.p;
     a.out_left = c.at<float>(c.sc.bb) + (size_t)i * L;
     a.out_right = a.out_left + (size_t)c.chunk * L;
     a.ir_len = (int64_t)L;
@@ -148,12 +148,8 @@ arx_status arx_render_listener_bands(arx_renderer* r, const arx_listener_pose* p
     c.N = n_rays(r->cfg);
     if (c.N == 0) return fail(ARX_ERR_NOT_READY, "a launch of no rays is not cacheable");
     ARX_HIP(hipSetDevice(r->cfg.device));
-    if (filters) {
-        ListenerScratch& lb = r->listener_bands;
-        const uint64_t need = (uint64_t)B * (uint64_t)taps * sizeof(double);
-        if (need > lb.filters_cap)
-            if (const arx_status st = grow_device(&lb.d_filters, &lb.filters_cap, need, 0, 1); st != ARX_OK) return st;
-    }
+    if (filters)
+        if (const arx_status st = r->listener_bands.d_filters.reserve((uint64_t)B * (uint64_t)taps); st != ARX_OK) return st;
     c.single.assign(n * (size_t)B, arx_band_result{});
     return run_listener_call(c, ms != nullptr, ms);  // timed around the whole call, its warm launches included
 }

@@ -91,20 +91,9 @@ void listener_entry_place(const arx_renderer* r, const ListenerSlots& s, int32_t
 
 // The chunk scratch of `need` bytes; false: no room (that size is not tried again).
 bool scratch_reserve(arx_renderer* r, ListenerScratch& lb, uint64_t need) {
-    if (lb.d_scratch && lb.scratch_bytes >= need) return true;
+    if (lb.d_scratch.p && need <= lb.d_scratch.cap) return true;
     if (known_no_room(lb.no_room, need) || sync_renderer(r) != ARX_OK) return false;
-    return grow_device_optional(&lb.d_scratch, &lb.scratch_bytes, need, need, &lb.no_room);
-}
-
-// The pinned block of `need` bytes.  Nothing of an earlier call is in flight: every call ends synchronised.
-arx_status pinned_reserve(ListenerScratch& lb, size_t need) {
-    if (need <= lb.h_bytes) return ARX_OK;
-    if (lb.h_pinned) hipHostFree(lb.h_pinned);
-    lb.h_pinned = nullptr;
-    lb.h_bytes = 0;
-    ARX_HIP(hipHostMalloc(&lb.h_pinned, need, hipHostMallocDefault));
-    lb.h_bytes = need;
-    return ARX_OK;
+    return lb.d_scratch.try_reserve(need, &lb.no_room);
 }
 
 // The tree's flag as the chunks left it: a box of the chunks' last tree write left the quantization grid.
@@ -141,7 +130,7 @@ arx_status prepare_batch(ListenerCall& c, bool* batch) {
     // the arrays may have moved and the grid grown: the replay's arguments as they stand now
     if ((st = trace_rays(r, 0, c.N, false, false, &c.probe)) != ARX_OK) return st;
     *batch = c.probe.ready;
-    c.d_base = static_cast<char*>(c.own->d_scratch);
+    c.d_base = c.own->d_scratch.p;
     c.fgrow = path_filter_grow(c.probe.args.qgrid);
     return ARX_OK;
 }
@@ -181,12 +170,12 @@ arx_status adopt_last_frame(ListenerCall& c, int32_t i) {
     arx_renderer::FrameSet& f = r->cur();
     const float* d_irl = c.at<float>(sc.ir) + (size_t)i * ir_len;
     const char* d_list = c.d_base + sc.lists + (uint64_t)i * sc.list_stride;
-    ARX_HIP(hipMemcpyAsync(f.d_hist, c.at<unsigned long long>(sc.hist) + (size_t)i * 2 * ir_len,
+    ARX_HIP(hipMemcpyAsync(f.d_hist.p, c.at<unsigned long long>(sc.hist) + (size_t)i * 2 * ir_len,
                            2 * ir_len * sizeof(unsigned long long), hipMemcpyDeviceToDevice, r->stream));
-    ARX_HIP(hipMemcpyAsync(f.d_counters, c.at<unsigned long long>(sc.counters) + (size_t)i * batch_counter_words(0),
+    ARX_HIP(hipMemcpyAsync(f.d_counters.p, c.at<unsigned long long>(sc.counters) + (size_t)i * batch_counter_words(0),
                            kCounters * sizeof(unsigned long long), hipMemcpyDeviceToDevice, r->stream));
-    ARX_HIP(hipMemcpyAsync(f.d_ir, d_irl, ir_len * sizeof(float), hipMemcpyDeviceToDevice, r->stream));
-    ARX_HIP(hipMemcpyAsync(f.d_ir + ir_len, d_irl + (size_t)c.chunk * ir_len, ir_len * sizeof(float), hipMemcpyDeviceToDevice,
+    ARX_HIP(hipMemcpyAsync(f.d_ir.p, d_irl, ir_len * sizeof(float), hipMemcpyDeviceToDevice, r->stream));
+    ARX_HIP(hipMemcpyAsync(f.d_ir.p + ir_len, d_irl + (size_t)c.chunk * ir_len, ir_len * sizeof(float), hipMemcpyDeviceToDevice,
                            r->stream));
     PathCache& pc = r->path_cache;
     pc.state = kPathReplayed;
@@ -194,8 +183,8 @@ arx_status adopt_last_frame(ListenerCall& c, int32_t i) {
     pc.last_valid = true;
     pc.last_filtered = false;
     if (path_filter_list_reserve(r, N)) {
-        ARX_HIP(hipMemcpyAsync(f.d_filter_list, d_list, N * sizeof(FilterCand), hipMemcpyDeviceToDevice, r->stream));
-        ARX_HIP(hipMemcpyAsync(static_cast<FilterCand*>(f.d_filter_list) + f.filter_list_cap, d_list + N * sizeof(FilterCand),
+        ARX_HIP(hipMemcpyAsync(f.d_filter_list.p, d_list, N * sizeof(FilterCand), hipMemcpyDeviceToDevice, r->stream));
+        ARX_HIP(hipMemcpyAsync(reinterpret_cast<FilterCand*>(f.d_filter_list.p) + f.filter_list_rays, d_list + N * sizeof(FilterCand),
                                16 * path_filter_heads(N), hipMemcpyDeviceToDevice, r->stream));
         pc.last_filtered = true;
         pc.filter_slot = r->slot;
@@ -219,7 +208,7 @@ arx_status queue_chunk_results(ListenerCall& c, size_t c0, int32_t J) {
     if (c.acoustics)
         ARX_HIP(hipMemcpyAsync(c.h_res + 3 * cells * c0, c.at<char>(c.sc.res), (size_t)J * cells * 3 * sizeof(arx_acoustics),
                                hipMemcpyDeviceToHost, r->stream));
-    ARX_HIP(hipMemcpyAsync(c.h_flag, r->d_tree_flag, sizeof(unsigned int), hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipMemcpyAsync(c.h_flag, r->d_tree_flag.p, sizeof(unsigned int), hipMemcpyDeviceToHost, r->stream));
     c.h_flag[1] = r->tree_gen;
     return ARX_OK;
 }
@@ -302,15 +291,15 @@ arx_status render_single(ListenerCall& c, size_t j) {
     const size_t ir_len = c.ir_len;
     c.where[j] = c.n + j;
     if (c.ir_left) {
-        ARX_HIP(hipMemcpyAsync(c.ir_left + j * ir_len, f.d_ir, ir_len * sizeof(float), hipMemcpyDefault, r->stream));
-        ARX_HIP(hipMemcpyAsync(c.ir_right + j * ir_len, f.d_ir + ir_len, ir_len * sizeof(float), hipMemcpyDefault,
+        ARX_HIP(hipMemcpyAsync(c.ir_left + j * ir_len, f.d_ir.p, ir_len * sizeof(float), hipMemcpyDefault, r->stream));
+        ARX_HIP(hipMemcpyAsync(c.ir_right + j * ir_len, f.d_ir.p + ir_len, ir_len * sizeof(float), hipMemcpyDefault,
                                r->stream));
     }
     unsigned long long* hc = c.h_counters + c.where[j] * batch_counter_words(0);
     hc[kCounters] = 0;
-    ARX_HIP(hipMemcpyAsync(hc, f.d_counters, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipMemcpyAsync(hc, f.d_counters.p, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, r->stream));
     if (c.acoustics)
-        ARX_HIP(hipMemcpyAsync(c.h_res + 3 * c.where[j], f.acou.d_res, 3 * sizeof(arx_acoustics), hipMemcpyDeviceToHost,
+        ARX_HIP(hipMemcpyAsync(c.h_res + 3 * c.where[j], f.acou.d_res.p, 3 * sizeof(arx_acoustics), hipMemcpyDeviceToHost,
                                r->stream));
     c.route[j] = ARX_LISTENER_SINGLE;
     return ARX_OK;
@@ -388,8 +377,9 @@ arx_status arx::run_listener_call(ListenerCall& c, bool timed, double* ms) {
     arx_status st;
     ARX_HIP(hipSetDevice(r->cfg.device));
     const BatchPinned pin = batch_pinned(c.n, c.bands);
-    if ((st = pinned_reserve(lb, pin.total)) != ARX_OK) return st;
-    char* const h = static_cast<char*>(lb.h_pinned);
+    // nothing of an earlier call is in flight: every call ends synchronised
+    if ((st = lb.h_pinned.reserve(pin.total)) != ARX_OK) return st;
+    char* const h = lb.h_pinned.p;
     c.h_entries = reinterpret_cast<ListenerEntry*>(h + pin.entries);
     c.h_counters = reinterpret_cast<unsigned long long*>(h + pin.counters);
     c.h_res = reinterpret_cast<arx_acoustics*>(h + pin.res);
@@ -405,16 +395,6 @@ arx_status arx::run_listener_call(ListenerCall& c, bool timed, double* ms) {
     if (st != ARX_OK || !timed) return st;
     if ((st = lb.timer.end(r->stream)) != ARX_OK) return st;
     return lb.timer.elapsed(ms);
-}
-
-void arx::free_listener_scratch(ListenerScratch& b) {
-    hipFree(b.d_scratch);
-    hipFree(b.d_filters);
-    if (b.h_pinned) hipHostFree(b.h_pinned);
-    b.timer.destroy();
-    const int32_t forced = b.forced_chunk;
-    b = ListenerScratch{};
-    b.forced_chunk = forced;
 }
 
 extern "C" {

@@ -22,9 +22,9 @@ namespace {
 bool path_filter_reserve(arx_renderer* r, uint64_t n, uint32_t max_bounces) {
     PathCache& pc = r->path_cache;
     const uint64_t need = path_filter_plane_bytes(n, max_bounces);
-    if (need <= pc.filter_cap) return true;
+    if (need <= pc.d_filter.cap) return true;
     if (known_no_room(pc.filter_no_room, need) || sync_renderer(r) != ARX_OK) return false;
-    return grow_device_optional(&pc.d_filter, &pc.filter_cap, need, need, &pc.filter_no_room);
+    return pc.d_filter.try_reserve(need, &pc.filter_no_room);
 }
 
 }  // namespace
@@ -35,26 +35,25 @@ arx_status arx::path_cache_reserve(arx_renderer* r, uint64_t n, uint64_t need, b
     if (!pc.ev_recorded) ARX_HIP(hipEventCreateWithFlags(&pc.ev_recorded, hipEventDisableTiming));
     for (hipEvent_t& e : pc.ev_replayed)
         if (!e) ARX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (!pc.d_scratch) ARX_HIP(hipMalloc(&pc.d_scratch, (kCursor + 1) * sizeof(unsigned long long)));
-    if (!pc.h_scratch) ARX_HIP(hipHostMalloc(&pc.h_scratch, kCounters * sizeof(unsigned long long), hipHostMallocDefault));
-    if (n <= pc.dirs_cap && need <= pc.cap_bytes) return ARX_OK;
-    const arx_status st = sync_renderer(r);
-    if (st != ARX_OK) return st;
+    arx_status st;
+    if ((st = pc.d_scratch.reserve(kCursor + 1)) != ARX_OK || (st = pc.h_scratch.reserve(kCounters)) != ARX_OK) return st;
+    if (n <= pc.d_dirs.cap && need <= pc.d_hits.cap) return ARX_OK;
+    if ((st = sync_renderer(r)) != ARX_OK) return st;
     // the caller marks the records' size as not fitting (PathCache::no_room), whichever buffer it was
-    *fits = (n <= pc.dirs_cap || grow_device_optional(&pc.d_dirs, &pc.dirs_cap, n, n * 16, &pc.no_room)) &&
-            (need <= pc.cap_bytes || grow_device_optional(&pc.d_hits, &pc.cap_bytes, need, need, &pc.no_room));
+    *fits = pc.d_dirs.try_reserve(n, &pc.no_room) && pc.d_hits.try_reserve(need, &pc.no_room);
     return ARX_OK;
 }
 
 bool arx::path_filter_list_reserve(arx_renderer* r, uint64_t n) {
     PathCache& pc = r->path_cache;
     arx_renderer::FrameSet& f = r->cur();
-    if (n <= f.filter_list_cap) return true;
+    if (n <= f.filter_list_rays) return true;
     const uint64_t need = path_filter_list_bytes(n);
     if (known_no_room(pc.filter_list_no_room, need)) return false;
     // an earlier replay on this set's stream may still write it
-    if (f.d_filter_list && hipStreamSynchronize(f.stream) != hipSuccess) return false;
-    return grow_device_optional(&f.d_filter_list, &f.filter_list_cap, n, need, &pc.filter_list_no_room);
+    if (f.d_filter_list.p && hipStreamSynchronize(f.stream) != hipSuccess) return false;
+    f.filter_list_rays = f.d_filter_list.try_reserve(need, &pc.filter_list_no_room) ? n : 0;
+    return f.filter_list_rays > 0;
 }
 
 float arx::path_filter_grow(const QGrid& g) {
@@ -62,25 +61,6 @@ float arx::path_filter_grow(const QGrid& g) {
     for (int k = 0; k < 3; ++k)
         m = std::max(m, std::max(std::fabs(g.origin[k]), std::fabs(g.origin[k] + 65536.0f * g.scale[k])));
     return kFilterMargin + std::ldexp(m, -18);
-}
-
-void arx::free_path_cache(PathCache& p) {
-    hipFree(p.d_dirs);
-    hipFree(p.d_hits);
-    hipFree(p.d_filter);
-    hipFree(p.d_scratch);
-    if (p.h_scratch) hipHostFree(p.h_scratch);
-    if (p.ev_recorded) hipEventDestroy(p.ev_recorded);
-    for (hipEvent_t e : p.ev_replayed)
-        if (e) hipEventDestroy(e);
-    const int32_t mode = p.mode, filter_on = p.filter_on;
-    const uint64_t max_bytes = p.max_bytes, rec_gen = p.rec_gen;
-    p = PathCache{};
-    p.rec_gen = rec_gen;  // never runs backwards: a plane made from freed directions stays stale
-    p.mode = mode;
-    p.filter_on = filter_on;
-    p.max_bytes = max_bytes;
-    p.state = mode == 1 ? kPathTraced : kPathOff;
 }
 
 namespace {
@@ -94,16 +74,16 @@ arx_status issue_path_record(arx_renderer* r, const TraceArgs& pa, uint64_t n_la
     for (int k = 0; k < r->fif; ++k)
         if (pc.replayed[k] && k != r->slot) ARX_HIP(hipStreamWaitEvent(r->stream, pc.ev_replayed[k], 0));
     for (bool& b : pc.replayed) b = false;
-    ARX_HIP(hipMemcpyAsync(pc.d_dirs, r->cur().d_dirs, n_launch * 16, hipMemcpyDeviceToDevice, r->stream));
+    ARX_HIP(hipMemcpyAsync(pc.d_dirs.p, r->cur().d_dirs.p, n_launch * 16, hipMemcpyDeviceToDevice, r->stream));
     TraceArgs ra = pa;
     ra.hist = nullptr;
-    ra.counters = pc.d_scratch;
-    ra.cursor = pc.d_scratch + kCursor;
+    ra.counters = pc.d_scratch.p;
+    ra.cursor = pc.d_scratch.p + kCursor;
     ra.clear_bins = 0;
     ra.clear_counters = kCounters;
     pc.has_state = pc.filter_on && pa.max_bounces >= 1 && pa.max_bounces <= kFilterMaxBounces &&
                    path_filter_reserve(r, n_launch, pa.max_bounces);
-    ra.gstack = pc.has_state ? static_cast<int32_t*>(pc.d_filter) : nullptr;
+    ra.gstack = pc.has_state ? reinterpret_cast<int32_t*>(pc.d_filter.p) : nullptr;
     ARX_HIP(launch_path_record(ra, grid_cus, r->stream));
     pc.recorded = true;
     pc.bytes = kPathRecordBytes * (uint64_t)pa.max_bounces * n_launch;
@@ -120,8 +100,8 @@ arx_status arx::issue_path_replay(arx_renderer* r, const TraceArgs& a, bool reco
     PathCache& pc = r->path_cache;
     arx_renderer::FrameSet& f = r->cur();
     TraceArgs pa = a;
-    pa.dirs = pc.d_dirs;
-    pa.rec = pc.d_hits;
+    pa.dirs = pc.d_dirs.p;
+    pa.rec = pc.d_hits.p;
     if (record) {
         if (const arx_status st = issue_path_record(r, pa, n_launch, grid_cus); st != ARX_OK) return st;
     } else if (pc.rec_stream != r->stream) {
@@ -134,9 +114,9 @@ arx_status arx::issue_path_replay(arx_renderer* r, const TraceArgs& a, bool reco
                           path_filter_list_reserve(r, n_launch);
     if (filtered) {
         FilterArgs fa;
-        fa.planes = pc.d_filter;
-        fa.list = static_cast<FilterCand*>(f.d_filter_list);
-        fa.heads = fa.list + f.filter_list_cap;
+        fa.planes = pc.d_filter.p;
+        fa.list = reinterpret_cast<FilterCand*>(f.d_filter_list.p);
+        fa.heads = fa.list + f.filter_list_rays;
         fa.grow = path_filter_grow(a.qgrid);
         ARX_HIP(launch_path_replay_filtered(pa, fa, r->stream));
         pc.last_filtered = true;
@@ -175,10 +155,10 @@ arx_status arx_debug_path_cache_state(arx_renderer* r, int32_t* state, uint64_t*
         *queries_recorded = 0;
         if (pc.recorded) {  // the recording's own query counter (its scratch block)
             ARX_HIP(hipSetDevice(r->cfg.device));
-            ARX_HIP(hipMemcpyAsync(pc.h_scratch, pc.d_scratch, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+            ARX_HIP(hipMemcpyAsync(pc.h_scratch.p, pc.d_scratch.p, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                    pc.rec_stream));
             ARX_HIP(hipStreamSynchronize(pc.rec_stream));
-            *queries_recorded = pc.h_scratch[0];
+            *queries_recorded = pc.h_scratch.p[0];
         }
     }
     return ARX_OK;
@@ -201,19 +181,19 @@ arx_status arx_debug_path_filter_state(arx_renderer* r, int32_t* filtered, uint6
     const PathCache& pc = r->path_cache;
     if (filtered) *filtered = pc.last_filtered ? 1 : 0;
     if (bytes) {
-        *bytes = pc.filter_cap;
+        *bytes = pc.d_filter.bytes();
         for (const arx_renderer::FrameSet& f : r->sets)
-            if (f.d_filter_list) *bytes += path_filter_list_bytes(f.filter_list_cap);
+            *bytes += f.d_filter_list.bytes();
     }
     if (candidate_rays) *candidate_rays = 0;
     if (candidate_queries) *candidate_queries = 0;
     const arx_renderer::FrameSet& f = r->sets[pc.filter_slot];
-    if ((candidate_rays || candidate_queries) && pc.last_filtered && f.d_filter_list) {
+    if ((candidate_rays || candidate_queries) && pc.last_filtered && f.d_filter_list.p) {
         // the heads the launch's filter blocks left behind the list: {candidate rays, candidate queries, ...}
         std::vector<uint32_t> h(4 * path_filter_heads(pc.filter_rays));
         ARX_HIP(hipSetDevice(r->cfg.device));
         ARX_HIP(hipStreamSynchronize(f.stream));
-        ARX_HIP(hipMemcpy(h.data(), static_cast<const FilterCand*>(f.d_filter_list) + f.filter_list_cap,
+        ARX_HIP(hipMemcpy(h.data(), reinterpret_cast<const FilterCand*>(f.d_filter_list.p) + f.filter_list_rays,
                           h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         uint64_t rays = 0, queries = 0;
         for (size_t k = 0; k < h.size(); k += 4) {

@@ -52,19 +52,19 @@ TraceArgs make_trace_args(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end,
     const arx_config& c = r->cfg;
     TraceArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.cnodes = r->d_cnodes;
+    a.cnodes = r->d_cnodes.p;
     // quantized nodes only while the emitter (the one ray origin off the geometry) is on the
     // grid: the slab arithmetic's error bound assumes origins within the grid's extent
     const float* em = r->emitter;
-    a.qnodes = (r->q_valid && !r->force_f32_nodes && qgrid_contains(r->qgrid, em, em)) ? r->d_qnodes : nullptr;
+    a.qnodes = (r->q_valid && !r->force_f32_nodes && qgrid_contains(r->qgrid, em, em)) ? r->d_qnodes.p : nullptr;
     // the CW4 tree on the same condition when asked for (arx_debug_set_trace_path bit 3; measured
     // 1.9x slower than the BVH2 on C3: DESIGN.md section 6.3)
-    a.wbuf = (a.qnodes && r->use_w4 && !r->force_global_stack) ? r->d_wbuf : nullptr;
+    a.wbuf = (a.qnodes && r->use_w4 && !r->force_global_stack) ? r->d_wbuf.p : nullptr;
     a.qgrid = r->qgrid;
-    a.tris = r->d_tris;
+    a.tris = r->d_tris.p;
     a.hist = r->hist();
-    a.counters = f.d_counters;
-    a.cursor = f.d_counters + kCursor;
+    a.counters = f.d_counters.p;
+    a.cursor = f.d_counters.p + kCursor;
     a.seed = c.seed;
     a.ray_begin = ray_begin;
     a.ray_end = ray_end;
@@ -96,9 +96,9 @@ TraceArgs make_trace_args(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end,
 // the CW4 tree) the renderer's global stack; *gstack: the launch takes it for a deep tree.
 arx_status reserve_launch_scratch(arx_renderer* r, TraceArgs& a, uint64_t n_launch, bool* gstack) {
     arx_renderer::FrameSet& f = r->cur();
-    if (n_launch > f.dirs_cap) {  // direction pre-pass buffer; what the old one held is forgotten
+    if (n_launch > f.d_dirs.cap) {  // direction pre-pass buffer; what the old one held is forgotten
         f.dirs_valid = f.dirs_sorted = false;
-        if (const arx_status st = grow_device(&f.d_dirs, &f.dirs_cap, n_launch, 0, 16); st != ARX_OK) return st;
+        if (const arx_status st = f.d_dirs.reserve(n_launch); st != ARX_OK) return st;
     }
     *gstack = r->force_global_stack || a.bvh_depth + 1 > kLdsStack;
     // CW4: up to three pushes per level; the rows beyond the LDS rows overflow into a global column
@@ -106,10 +106,8 @@ arx_status reserve_launch_scratch(arx_renderer* r, TraceArgs& a, uint64_t n_laun
     if (*gstack || a.wbuf) {  // one global column of bvh_depth + 1 entries per lane
         const size_t lanes = trace_max_lanes(r->cus);
         const size_t need = (a.wbuf ? w4_rows : (size_t)(a.bvh_depth + 1)) * lanes;
-        if (need > r->gstack_cap)
-            if (const arx_status st = grow_device(&r->d_gstack, &r->gstack_cap, need, 0, sizeof(int32_t)); st != ARX_OK)
-                return st;
-        a.gstack = r->d_gstack;
+        if (const arx_status st = r->d_gstack.reserve(need); st != ARX_OK) return st;
+        a.gstack = r->d_gstack.p;
         a.gstack_lanes = lanes;
         // one global stack per renderer: with frames in flight, after the other frames' traces
         if (const arx_status w = fif_wait_traced(r); w != ARX_OK) return w;
@@ -117,12 +115,9 @@ arx_status reserve_launch_scratch(arx_renderer* r, TraceArgs& a, uint64_t n_laun
 #if ARX_TRACE_PROF  // measurement builds only: per-wave records (arx_debug_trace_profile)
     {
         const size_t words = (size_t)r->cus * 64 * kProfWords;  // >= waves of any trace grid
-        if (!r->d_prof) {
-            ARX_HIP(hipMalloc(&r->d_prof, words * sizeof(unsigned long long)));
-            r->prof_words = words;
-        }
-        ARX_HIP(hipMemsetAsync(r->d_prof, 0, words * sizeof(unsigned long long), r->stream));
-        a.prof = r->d_prof;
+        if (const arx_status st = r->d_prof.reserve(words); st != ARX_OK) return st;
+        ARX_HIP(hipMemsetAsync(r->d_prof.p, 0, words * sizeof(unsigned long long), r->stream));
+        a.prof = r->d_prof.p;
     }
 #endif
     return ARX_OK;
@@ -169,11 +164,11 @@ arx_status plan_ray_order(arx_renderer* r, const TraceArgs& a, const OrderKey& k
     o->use_sorted = ordered && kept && f.dirs_sorted && same_key(key, f.order_key);
     o->measure = ordered && !o->use_sorted;
     o->fill_dirs = !o->use_sorted && !(kept && !f.dirs_sorted);
-    if (o->measure && f.order_cap != f.dirs_cap) {  // the two buffers swap: always the same size
+    if (o->measure) {  // the two direction buffers swap: always the same size
         arx_status st;
-        if (!f.d_order_bins) ARX_HIP(hipMalloc(&f.d_order_bins, order_bins_bytes()));
-        if ((st = grow_device(&f.d_dirs_alt, &f.order_cap, f.dirs_cap, 0, 16)) != ARX_OK) return st;
-        if ((st = grow_device(&f.d_cost, &f.order_cap, f.dirs_cap, 0, sizeof(unsigned short))) != ARX_OK) return st;
+        if ((st = f.d_order_bins.reserve(order_bins_bytes() / sizeof(uint32_t))) != ARX_OK || (st = f.d_dirs_alt.reserve(f.d_dirs.cap)) != ARX_OK ||
+            (st = f.d_cost.reserve(f.d_dirs.cap)) != ARX_OK)
+            return st;
     }
     return ARX_OK;
 }
@@ -202,7 +197,7 @@ arx_status issue_trace(arx_renderer* r, const TraceArgs& a, const OrderKey& key,
     f.dirs_count = n_launch;
     f.dirs_sorted = o.use_sorted;
     if (o.measure) {  // inside the launch's timing window: a cost this frame pays
-        ARX_HIP(launch_order_pool(f.d_dirs, f.d_dirs_alt, f.d_cost, f.d_order_bins, n_launch, r->stream));
+        ARX_HIP(launch_order_pool(f.d_dirs.p, f.d_dirs_alt.p, f.d_cost.p, f.d_order_bins.p, n_launch, r->stream));
         std::swap(f.d_dirs, f.d_dirs_alt);
         f.order_key = key;
         f.dirs_sorted = true;
@@ -230,7 +225,7 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     TraceArgs a = make_trace_args(r, ray_begin, ray_end, clear);
     if (ray_end == ray_begin) {  // nothing to trace: the clear alone
         if (probe) return ARX_OK;
-        if (clear) ARX_HIP(launch_clear(r->hist(), 2 * (uint64_t)r->ir_len, f.d_counters, (int)kCounters, r->stream));
+        if (clear) ARX_HIP(launch_clear(r->hist(), 2 * (uint64_t)r->ir_len, f.d_counters.p, (int)kCounters, r->stream));
         return ARX_OK;
     }
     const uint64_t n_launch = ray_end - ray_begin;
@@ -245,8 +240,8 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
     const OrderKey key = make_order_key(r, a, fmt);
     RayOrder order;
     if ((st = plan_ray_order(r, a, key, n_launch, &order)) != ARX_OK) return st;
-    a.dirs = f.d_dirs;
-    a.cost = order.measure ? f.d_cost : nullptr;
+    a.dirs = f.d_dirs.p;
+    a.cost = order.measure ? f.d_cost.p : nullptr;
     const int inst = order.measure ? kInstMeasure : (small ? kInstSmall : kInstPool);
     r->stats.trace_format = fmt;
     r->stats.trace_vgprs = r->occ[fmt][inst][0];
@@ -277,12 +272,12 @@ arx_status arx::trace_rays(arx_renderer* r, uint64_t ray_begin, uint64_t ray_end
         // records of another key: those are dropped now (arx_debug_path_cache_state reports 0 bytes)
         pc.recorded = plan.recorded;
         probe->recorded = plan.replay && !plan.record && pc.rec_stream == r->stream;
-        probe->ready = probe->recorded && pc.filter_on && pc.has_state && pc.d_filter;
+        probe->ready = probe->recorded && pc.filter_on && pc.has_state && pc.d_filter.p;
         probe->state = plan.state;
         probe->args = a;
-        probe->args.dirs = pc.d_dirs;
-        probe->args.rec = pc.d_hits;
-        probe->planes = pc.d_filter;
+        probe->args.dirs = pc.d_dirs.p;
+        probe->args.rec = pc.d_hits.p;
+        probe->planes = pc.d_filter.p;
         return ARX_OK;
     }
     pc.last_filtered = false;
@@ -312,7 +307,7 @@ extern "C" {
 arx_status arx_finalize_ir(arx_renderer* r) {
     if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
     ARX_HIP(hipSetDevice(r->cfg.device));
-    ARX_HIP(launch_finalize_ir((const long long*)r->hist(), r->cur().d_ir, r->cur().d_ir + r->ir_len, r->ir_len,
+    ARX_HIP(launch_finalize_ir((const long long*)r->hist(), r->cur().d_ir.p, r->cur().d_ir.p + r->ir_len, r->ir_len,
                                ir_unit(r->cfg), r->cfg.is_mono, r->stream));
     r->conv_ir_dirty = true;
     r->conv_live_ir_dirty = true;
@@ -324,19 +319,17 @@ arx_status arx_analyze_ir(arx_renderer* r) {
     if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
     ARX_HIP(hipSetDevice(r->cfg.device));
     arx_renderer::Acoustics& a = r->cur().acou;
-    if (!a.d_edc) {  // this frame set's first analysis
-        hipError_t e;
-        if ((e = hipMalloc(&a.d_edc, 3 * (size_t)r->ir_len * sizeof(long long))) != hipSuccess ||
-            (e = hipMalloc(&a.d_res, 3 * sizeof(arx_acoustics))) != hipSuccess ||
-            (e = hipMalloc(&a.d_scratch, acoustics_scratch_bytes())) != hipSuccess) {
-            free_acoustics(a);
-            return fail(e == hipErrorOutOfMemory ? ARX_ERR_OUT_OF_MEMORY : ARX_ERR_HIP, "arx_analyze_ir: %s",
-                        hipGetErrorString(e));
+    if (!a.d_edc.p) {  // this frame set's first analysis
+        arx_status st;
+        if ((st = a.d_edc.reserve(3 * (size_t)r->ir_len)) != ARX_OK || (st = a.d_res.reserve(3)) != ARX_OK ||
+            (st = a.d_scratch.reserve(acoustics_scratch_bytes())) != ARX_OK) {
+            a.release();
+            return st;
         }
     }
     if (r->timing)
         if (const arx_status st = r->analysis_ring.begin(r->stream); st != ARX_OK) return st;
-    ARX_HIP(launch_acoustics(acoustics_args(r, (const long long*)r->hist(), a.d_edc, a.d_res, a.d_scratch), r->stream));
+    ARX_HIP(launch_acoustics(acoustics_args(r, (const long long*)r->hist(), a.d_edc.p, a.d_res.p, a.d_scratch.p), r->stream));
     if (r->timing)
         if (const arx_status st = r->analysis_ring.end(r->stream); st != ARX_OK) return st;
     a.queued = true;
@@ -347,7 +340,7 @@ arx_status arx_clear_histogram(arx_renderer* r) {
     if (!r) return fail(ARX_ERR_INVALID_ARGUMENT, "renderer is NULL");
     const arx_status st = arx::begin_frame(r);
     if (st != ARX_OK) return st;
-    ARX_HIP(launch_clear(r->hist(), 2 * (uint64_t)r->ir_len, r->cur().d_counters, (int)kCounters, r->stream));
+    ARX_HIP(launch_clear(r->hist(), 2 * (uint64_t)r->ir_len, r->cur().d_counters.p, (int)kCounters, r->stream));
     return ARX_OK;
 }
 
@@ -393,14 +386,14 @@ arx_status arx_get_acoustics(arx_renderer* r, int32_t channel, arx_acoustics* ou
     if (channel < 0 || channel > 2) return fail(ARX_ERR_INVALID_ARGUMENT, "channel %d: 0 left, 1 right, 2 sum", channel);
     if (!r->cur().acou.queued) return fail(ARX_ERR_NOT_READY, "no analysis was queued for the last frame (arx_analyze_ir)");
     ARX_HIP(hipSetDevice(r->cfg.device));
-    ARX_HIP(hipMemcpyAsync(out, r->cur().acou.d_res + channel, sizeof(arx_acoustics), hipMemcpyDeviceToHost, r->stream));
+    ARX_HIP(hipMemcpyAsync(out, r->cur().acou.d_res.p + channel, sizeof(arx_acoustics), hipMemcpyDeviceToHost, r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));
     return ARX_OK;
 }
 
 arx_status arx_edc_device(arx_renderer* r, int64_t** d_edc, size_t* n) {
     if (!r || !d_edc) return fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
-    *d_edc = (int64_t*)r->cur().acou.d_edc;
+    *d_edc = (int64_t*)r->cur().acou.d_edc.p;
     if (n) *n = 3 * (size_t)r->ir_len;
     return ARX_OK;
 }
@@ -411,7 +404,7 @@ arx_status arx_copy_edc(arx_renderer* r, int32_t channel, int64_t* h_edc, size_t
     if (ir_len != (size_t)r->ir_len) return fail(ARX_ERR_INVALID_ARGUMENT, "ir_len %zu != %d", ir_len, r->ir_len);
     if (!r->cur().acou.queued) return fail(ARX_ERR_NOT_READY, "no analysis was queued for the last frame (arx_analyze_ir)");
     ARX_HIP(hipSetDevice(r->cfg.device));
-    ARX_HIP(hipMemcpyAsync(h_edc, r->cur().acou.d_edc + (size_t)channel * ir_len, ir_len * sizeof(int64_t),
+    ARX_HIP(hipMemcpyAsync(h_edc, r->cur().acou.d_edc.p + (size_t)channel * ir_len, ir_len * sizeof(int64_t),
                            hipMemcpyDeviceToHost, r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));
     return ARX_OK;
@@ -421,21 +414,21 @@ arx_status arx_debug_trace_counters(arx_renderer* r, uint64_t* out, size_t n) {
     if (!r || !out || n > (size_t)kCounters) return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
     ARX_HIP(hipSetDevice(r->cfg.device));
     const arx_renderer::FrameSet& f = r->cur();
-    ARX_HIP(hipMemcpyAsync(f.h_counters, f.d_counters, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+    ARX_HIP(hipMemcpyAsync(f.h_counters.p, f.d_counters.p, kCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                            r->stream));
     ARX_HIP(hipStreamSynchronize(r->stream));
-    for (size_t i = 0; i < n; ++i) out[i] = f.h_counters[i];
+    for (size_t i = 0; i < n; ++i) out[i] = f.h_counters.p[i];
     return ARX_OK;
 }
 
 
 arx_status arx_debug_trace_profile(arx_renderer* r, uint64_t* out, size_t n_words, size_t* n_out) {
     if (!r || (n_words > 0 && !out)) return fail(ARX_ERR_INVALID_ARGUMENT, "bad arguments");
-    if (!r->d_prof) return fail(ARX_ERR_NOT_READY, "not a profiling build (ARX_TRACE_PROF) or no trace yet");
+    if (!r->d_prof.p) return fail(ARX_ERR_NOT_READY, "not a profiling build (ARX_TRACE_PROF) or no trace yet");
     ARX_HIP(hipSetDevice(r->cfg.device));
     ARX_HIP(hipStreamSynchronize(r->stream));
-    const size_t k = std::min(n_words, r->prof_words);
-    ARX_HIP(hipMemcpy(out, r->d_prof, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    const size_t k = std::min<size_t>(n_words, r->d_prof.cap);
+    ARX_HIP(hipMemcpy(out, r->d_prof.p, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (n_out) *n_out = k;
     return ARX_OK;
 }
@@ -469,7 +462,7 @@ arx_status arx_debug_ray_order_buffer(arx_renderer* r, float* h_out_xyzw, uint64
     if (count > f.dirs_count) return fail(ARX_ERR_INVALID_ARGUMENT, "the buffer holds %llu rays", (unsigned long long)f.dirs_count);
     ARX_HIP(hipSetDevice(r->cfg.device));
     ARX_HIP(hipStreamSynchronize(r->stream));
-    if (count > 0) ARX_HIP(hipMemcpy(h_out_xyzw, f.d_dirs, count * 16, hipMemcpyDeviceToHost));
+    if (count > 0) ARX_HIP(hipMemcpy(h_out_xyzw, f.d_dirs.p, count * 16, hipMemcpyDeviceToHost));
     if (first_ray) *first_ray = f.dirs_begin;
     if (n_static) *n_static = f.dirs_sorted ? pool_static_rays(f.dirs_count, trace_pool_share()) : f.dirs_count;
     if (sorted) *sorted = f.dirs_sorted ? 1 : 0;

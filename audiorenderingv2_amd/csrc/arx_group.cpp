@@ -596,15 +596,7 @@ arx_status arx_group_convolute_audio_file(arx_group* g, const float* h_in, size_
         ARX_HIP(hipEventCreate(&p1));
         ev.e.emplace_back(r->cfg.device, p1);
         ARX_HIP(hipEventRecord(p0, r->stream));
-        if (n > r->conv_cap) {
-            hipFree(r->d_conv_in);
-            hipFree(r->d_conv_out);
-            r->d_conv_in = r->d_conv_out = nullptr;
-            r->conv_cap = 0;
-            ARX_HIP(hipMalloc(&r->d_conv_in, n * sizeof(float)));
-            ARX_HIP(hipMalloc(&r->d_conv_out, 2 * n * sizeof(float)));
-            r->conv_cap = n;
-        }
+        if (const arx_status rs = reserve_conv_staging(r, n); rs != ARX_OK) return rs;
         uint64_t pb = 0, pe = 0, b = 0, e = 0;
         conv_pairs_of(sr, n, rank, g->n_ranks, &pb, &pe);
         arx_group_conv_shard(sr, n, rank, g->n_ranks, &b, &e);
@@ -613,16 +605,16 @@ arx_status arx_group_convolute_audio_file(arx_group* g, const float* h_in, size_
         const uint64_t in_lo = std::min<uint64_t>(pb > 0 ? 2 * (pb - 1) * (uint64_t)sr : 0, n);
         const uint64_t in_hi = (pe > pb && S > 0) ? std::min<uint64_t>(2 * pe * (uint64_t)sr, n) : in_lo;
         if (in_hi > in_lo)
-            ARX_HIP(hipMemcpyAsync(r->d_conv_in + in_lo, h_in + in_lo, (in_hi - in_lo) * sizeof(float),
+            ARX_HIP(hipMemcpyAsync(r->d_conv_in.p + in_lo, h_in + in_lo, (in_hi - in_lo) * sizeof(float),
                                    hipMemcpyHostToDevice, r->stream));
         // timed when asked for the convolution's own window
-        const arx_status st = convolute_pairs(r, r->d_conv_in, n, r->d_conv_out, r->d_conv_out + n, (int64_t)pb,
+        const arx_status st = convolute_pairs(r, r->d_conv_in.p, n, r->d_conv_out.p, r->d_conv_out.p + n, (int64_t)pb,
                                               (int64_t)pe, r->timing || convolute_ms != nullptr);
         if (st != ARX_OK) return st;
         if (e > b) {  // this rank's output frames back into the caller's buffers
-            ARX_HIP(hipMemcpyAsync(h_out_left + b, r->d_conv_out + b, (e - b) * sizeof(float), hipMemcpyDeviceToHost,
+            ARX_HIP(hipMemcpyAsync(h_out_left + b, r->d_conv_out.p + b, (e - b) * sizeof(float), hipMemcpyDeviceToHost,
                                    r->stream));
-            ARX_HIP(hipMemcpyAsync(h_out_right + b, r->d_conv_out + n + b, (e - b) * sizeof(float),
+            ARX_HIP(hipMemcpyAsync(h_out_right + b, r->d_conv_out.p + n + b, (e - b) * sizeof(float),
                                    hipMemcpyDeviceToHost, r->stream));
         }
         ARX_HIP(hipEventRecord(p1, r->stream));

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <mutex>
@@ -36,6 +37,10 @@ arx_status fail(arx_status s, const char* fmt, ...) __attribute__((format(printf
             return ::arx::fail(e_ == hipErrorOutOfMemory ? ARX_ERR_OUT_OF_MEMORY : ARX_ERR_HIP,             \
                                "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);   \
     } while (0)
+
+}  // namespace arx
+#include "arx_device_mem.hpp"
+namespace arx {
 
 // device counters (per frame set, cleared by each frame): [0] queries [1] receiver hits [2] misses
 // [3] error flag [4..7] counting builds (node steps, triangle tests, leader-node steps, step slots); the trace launch's ray-pool cursor lives after
@@ -119,16 +124,14 @@ struct PathCache {
     bool recorded = false;
     OrderKey last_key{};   // ... and of the previous launch (last_valid), whatever ran for it
     bool last_valid = false;
-    void* d_dirs = nullptr;       // the direction buffer the records index, 16 B per ray
-    void* d_hits = nullptr;       // [bounce][slot] 16-B records, then [bounce][slot] 8-B records
-    uint64_t cap_bytes = 0;       // of d_hits
-    uint64_t dirs_cap = 0;        // rays of d_dirs
+    DeviceBuf<float4> d_dirs;     // the direction buffer the records index, one per ray
+    DeviceBuf<char> d_hits;       // [bounce][slot] 16-B records, then [bounce][slot] 8-B records
     uint64_t bytes = 0;           // of the records in use (recorded)
     uint64_t rec_rays = 0;        // rays of the records in use
     uint64_t rec_gen = 0;         // recordings made so far: what was derived from d_dirs is stale once it moves
     uint64_t no_room = 0;         // > 0: records of this size did not fit on the device (treated as over the cap)
-    unsigned long long* d_scratch = nullptr;  // the recording's counters and pool cursor (kCursor + 1 words)
-    unsigned long long* h_scratch = nullptr;  // pinned, kCounters words
+    DeviceBuf<unsigned long long> d_scratch;  // the recording's counters and pool cursor (kCursor + 1 words)
+    PinnedBuf<unsigned long long> h_scratch;  // kCounters words
     hipStream_t rec_stream = nullptr;         // the stream of the recording
     // frames in flight: a replay on another set's stream waits for `recorded`; a new recording waits
     // for every set's last replay
@@ -138,16 +141,33 @@ struct PathCache {
     // started from (path_filter_plane_bytes, arx_layout.hpp), outside the cap.  has_state: the records in
     // use came with them.  The candidate lists belong to the frame sets (FrameSet::d_filter_list).
     int32_t filter_on = ARX_PATH_FILTER_DEFAULT;
-    void* d_filter = nullptr;
-    uint64_t filter_cap = 0;          // bytes of d_filter
+    DeviceBuf<char> d_filter;
     uint64_t filter_no_room = 0;      // > 0: planes of this size did not fit on the device: not tried again ...
     uint64_t filter_list_no_room = 0; // ... and a frame set's list of this size, a mark of its own (a list is far smaller)
     bool has_state = false;
     bool last_filtered = false;       // the last launch replayed filtered ...
     int32_t filter_slot = 0;          // ... on this frame set ...
     uint64_t filter_rays = 0;         // ... over this many rays
+    // mode, max_bytes, filter_on and rec_gen stay (rec_gen never runs backwards: a plane made from freed
+    // directions stays stale)
+    void release() {
+        d_dirs.release();
+        d_hits.release();
+        d_filter.release();
+        d_scratch.release();
+        h_scratch.release();
+        if (ev_recorded) (void)hipEventDestroy(ev_recorded);
+        ev_recorded = nullptr;
+        for (hipEvent_t& e : ev_replayed) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        for (bool& b : replayed) b = false;
+        recorded = last_valid = has_state = last_filtered = false;
+        bytes = rec_rays = no_room = filter_no_room = filter_list_no_room = 0;
+        state = mode == 1 ? kPathTraced : kPathOff;
+    }
 };
-void free_path_cache(PathCache& p);
 // The cache's buffers for a recording of n rays and `need` bytes of records: made at the first recording
 // and kept across keys; a buffer that must grow is freed once every frame set's stream is idle (a replay
 // of the key before may still read it).  *fits false: the device has no room for them (the cache is
@@ -163,38 +183,6 @@ float path_filter_grow(const QGrid& g);
 // of n_launch rays with the launch's arguments a -- filtered where the filter's state allows it -- and
 // PathCache::state set to what ran.
 arx_status issue_path_replay(arx_renderer* r, const TraceArgs& a, bool record, uint64_t n_launch, int grid_cus);
-
-// A device buffer that must grow (mandatory): the old one freed, then room for count + slack elements;
-// *cap counts elements and is 0 while there is no buffer.  The caller has made sure nothing in flight
-// still uses the old buffer.  Two buffers of one capacity take one call each.
-template <class T, class Cap>
-arx_status grow_device(T** p, Cap* cap, size_t count, size_t slack, size_t elem_bytes) {
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    ARX_HIP(hipMalloc(p, (count + slack) * elem_bytes));
-    *cap = (Cap)(count + slack);
-    return ARX_OK;
-}
-// An optional buffer (the path cache, its filter, a batch's scratch) that must grow to `bytes`, which *cap
-// counts as `units`.  False: no room on the device -- the error cleared, the pointer null, *no_room the
-// size that did not fit; a size at or above *no_room is not tried.  Synchronisation as above.
-inline bool known_no_room(uint64_t no_room, uint64_t bytes) { return no_room > 0 && bytes >= no_room; }
-template <class T>
-bool grow_device_optional(T** p, uint64_t* cap, uint64_t units, uint64_t bytes, uint64_t* no_room) {
-    if (known_no_room(*no_room, bytes)) return false;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        *no_room = bytes;
-        return false;
-    }
-    *cap = units;
-    return true;
-}
 
 // The device time of one call: an event pair made at first use.  begin and end record on s; elapsed waits
 // for the end event.  Each call keeps its own rule for when it is timed and where its end lies.
@@ -232,16 +220,19 @@ struct CallTimer {
 // first batched call widens.
 struct ListenerScratch {
     int32_t forced_chunk = 0;     // arx_debug_set_listener_chunk: 0 automatic (`listeners` holds it for both calls)
-    void* d_scratch = nullptr;
-    uint64_t scratch_bytes = 0;
+    DeviceBuf<char> d_scratch;
     uint64_t no_room = 0;         // > 0: a scratch of this size did not fit on the device: not tried again
-    void* h_pinned = nullptr;     // per listener of a call: its table entry, counter words and results
-    size_t h_bytes = 0;
-    void* d_filters = nullptr;    // the band call's filter bank (n_bands x taps f64)
-    uint64_t filters_cap = 0;     // bytes
+    PinnedBuf<char> h_pinned;     // per listener of a call: its table entry, counter words and results
+    DeviceBuf<double> d_filters;  // the band call's filter bank (n_bands x taps)
     CallTimer timer;
+    void release() {              // forced_chunk stays
+        d_scratch.release();
+        h_pinned.release();
+        d_filters.release();
+        timer.destroy();
+        no_room = 0;
+    }
 };
-void free_listener_scratch(ListenerScratch& b);  // forced_chunk survives
 // What a chunk of receiver slots is laid out from: the receiver's and the renderer's own tree sizes, and the chunk.
 struct ListenerSlots {
     int64_t recv_nodes = 0, recv_tris = 0, own_nodes = 0, own_tris = 0;
@@ -324,18 +315,21 @@ arx_status run_listener_call(ListenerCall& c, bool timed, double* ms);
 // at arx_destroy; outside the path cache's cap.
 struct WalkScratch {
     int32_t forced_tile = 0;      // arx_debug_set_walk_tile: 0 the product's tile
-    void* d_scratch = nullptr;
-    uint64_t bytes = 0;
+    DeviceBuf<char> d_scratch;
     int32_t tw_n = 0;             // the scratch holds the twiddles of this FFT size (0: none)
     std::vector<double> h_tw;     // their host copy (2 doubles each)
     std::vector<int32_t> h_tables, h_slot;  // a call's item tables and IR slots, reused
     std::vector<double> h_w;      // and its fade weights
     CallTimer timer;              // the call's device time
     uint64_t state[5] = {};       // arx_debug_walk_state
+    void release() {              // forced_tile stays
+        d_scratch.release();
+        timer.destroy();
+        tw_n = 0;
+    }
 };
 constexpr int32_t kWalkTile = 8;      // items per MAC workgroup
 constexpr int32_t kWalkTileMax = 64;  // arx_debug_set_walk_tile
-void free_walk(WalkScratch& w);
 // Frequency-band absorption (arx_set_band_absorption / arx_render_bands, include/arx.h): the device table
 // ([triangle][band_width] f32, by global triangle id) and the call's scratch (band_scratch_layout,
 // arx_bands.hpp) -- one allocation each, kept across calls, freed when they must grow and at arx_destroy;
@@ -343,16 +337,20 @@ void free_walk(WalkScratch& w);
 struct BandState {
     int32_t n_bands = 0;          // 0: no table
     int64_t n_tris = 0;           // the table's rows
-    float* d_table = nullptr;
-    uint64_t table_cap = 0;       // bytes of d_table
-    void* d_scratch = nullptr;
-    uint64_t scratch_cap = 0;     // bytes of d_scratch
-    void* h_pinned = nullptr;     // kMaxBands counter blocks, then kMaxBands x 3 arx_acoustics
+    DeviceBuf<float> d_table;
+    DeviceBuf<char> d_scratch;
+    PinnedBuf<char> h_pinned;     // kMaxBands counter blocks, then kMaxBands x 3 arx_acoustics
     CallTimer timer;              // the call's device time
     int32_t hist_bands = 0;       // the scratch holds the raw histograms of this many bands (the last call's) ...
     int32_t hist_ir_len = 0;      // ... of this length (arx_debug_band_histograms)
+    void release() {
+        d_table.release();
+        d_scratch.release();
+        h_pinned.release();
+        timer.destroy();
+        n_bands = hist_bands = 0;
+    }
 };
-void free_bands(BandState& b);
 // Source directivity (arx_set_source_directivity / arx_set_source_orientation, include/arx.h): the pattern's
 // cube map on the device, the orientation, and the gain plane the directed band replays read
 // (arx_directivity.hpp) -- one allocation each, kept across calls, freed when they must grow and at
@@ -363,17 +361,20 @@ struct DirectivityState {
     int32_t n_bands = 0;          // 0: no pattern (the band replays run undirected); 1 serves every band
     int32_t res = 0;
     float m[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    float* d_cube = nullptr;
-    uint64_t cube_cap = 0;        // bytes of d_cube
-    float* d_plane = nullptr;
-    uint64_t plane_cap = 0;       // bytes of d_plane
+    DeviceBuf<float> d_cube;
+    DeviceBuf<float> d_plane;
     uint64_t pattern_gen = 0, orient_gen = 0;
     bool plane_valid = false;     // d_plane holds the plane of made_*
     uint64_t made_pattern = 0, made_orient = 0, made_rec = 0, made_rays = 0;
     int32_t made_bands = 0;
     uint64_t planes_made = 0;     // gain kernel launches so far
+    void release() {
+        d_cube.release();
+        d_plane.release();
+        n_bands = 0;
+        plane_valid = false;
+    }
 };
-void free_directivity(DirectivityState& d);
 // The rule of a band call with a pattern installed: a pattern of more than one band matches the table's bands.
 arx_status directivity_check_bands(const arx_renderer* r, int32_t n_bands);
 // The gain plane for a band call of n_bands bands over the recording whose direction copy is `dirs` (n rays),
@@ -384,11 +385,13 @@ arx_status directivity_plane(arx_renderer* r, const void* dirs, uint64_t n, int3
 // filters and outputs), made by the first call, kept across calls and freed when it must grow and at
 // arx_destroy; outside the path cache's cap.
 struct SynthScratch {
-    void* d_scratch = nullptr;
-    uint64_t bytes = 0;
+    DeviceBuf<char> d_scratch;
     CallTimer timer;              // the call's device time
+    void release() {
+        d_scratch.release();
+        timer.destroy();
+    }
 };
-void free_synth(SynthScratch& s);
 // A band call's recording (arx_render_bands, arx_render_listener_bands): ordinary launches -- the first at
 // *pose, when one is given -- until the cache holds the key's records (*probe says so); *warm counts them.
 arx_status record_for_bands(arx_renderer* r, uint64_t N, const arx_listener_pose* pose, ReplayProbe* probe, int32_t* warm);
@@ -471,6 +474,9 @@ arx_status sync_renderer(arx_renderer* r);
 // (conv_run_pairs; the group's time-block shards); timed: recorded in the file-convolution ring.
 arx_status convolute_pairs(arx_renderer* r, const float* d_in, size_t n_frames, float* d_out_left, float* d_out_right,
                            int64_t pair_begin, int64_t pair_end, bool timed);
+// The renderer's staging for a file convolution of n frames (arx_convolute_audio_file, the group's): n floats
+// in, 2 * n out; both replaced when either is too small.  The caller has waited for the last convolution.
+arx_status reserve_conv_staging(arx_renderer* r, size_t n);
 // Whether the renderer's file convolution plan convolves a shard on its own (conv_plan_shards).
 bool conv_shards(arx_renderer* r);
 // Detach a streaming convolution from its renderer and release its device side (arx_destroy).
@@ -503,24 +509,22 @@ struct arx_renderer {
     // receiver sub-tree in its local frame (refit path) and its device images
     bool recv_refit = true;
     float recv_radius = 0.0f;
-    arx::TriRec* d_recv_local = nullptr;
-    arx::BvhNode* d_recv_nodes = nullptr;
-    int32_t* d_recv_levels = nullptr;  // level-ordered node indices, then level starts
+    arx::DeviceBuf<arx::TriRec> d_recv_local;
+    arx::DeviceBuf<arx::BvhNode> d_recv_nodes;
+    arx::DeviceBuf<int32_t> d_recv_levels;  // level-ordered node indices, then level starts
     int32_t recv_levels = 0, recv_level_count = 0;
 
     // device
-    arx::BvhNode* d_cnodes = nullptr;  // coded copy of the tree (code_nodes): the f32 fallback
-    arx::QNode2* d_qnodes = nullptr;   // 16-bit quantized copy of d_cnodes (same indices): the default
+    arx::DeviceBuf<arx::BvhNode> d_cnodes;  // coded copy of the tree (code_nodes): the f32 fallback
+    arx::DeviceBuf<arx::QNode2> d_qnodes;   // 16-bit quantized copy of d_cnodes (same indices and size): the default
     // CW4 copy: buffer, f32 node records (top node, scene, host-built receiver) for the device
     // re-quantization, the receiver's CW4 layout (refit path) and its device tables
-    uint4* d_wbuf = nullptr;
-    size_t wbuf_cap = 0;           // units
-    arx::W4NodeF* d_w4f = nullptr;
-    size_t w4f_cap = 0;
+    arx::DeviceBuf<uint4> d_wbuf;  // units
+    arx::DeviceBuf<arx::W4NodeF> d_w4f;
     size_t n_w4f = 0;              // records in use
     arx::W4Build recv4;
-    int32_t* d_recv_w4 = nullptr;  // 11 ints per receiver CW4 node
-    int32_t* d_recv_w4_tris = nullptr;
+    arx::DeviceBuf<int32_t> d_recv_w4;  // 11 ints per receiver CW4 node
+    arx::DeviceBuf<int32_t> d_recv_w4_tris;
     bool use_w4 = false;           // arx_debug_set_trace_path bit 3: the CW4 tree
     int32_t depth4 = 0;            // CW4 levels (top node included): bounds the stack (3 per level)
     int32_t occ[3][3][3] = {};     // per node format and instance (kInstPool, kInstSmall, kInstMeasure): VGPRs, waves admitted, waves targeted
@@ -537,36 +541,33 @@ struct arx_renderer {
     bool qgrid_set = false;
     bool q_valid = false;         // d_qnodes matches the tree (re-quantized on the device, arx_receiver.hip)
     uint64_t requants = 0;        // device re-quantizations issued (new scene or grid)
-    size_t nodes_cap = 0;
-    arx::TriRec* d_tris = nullptr;
-    size_t tris_cap = 0;
-    int32_t* d_gstack = nullptr;  // global traversal stack for trees deeper than the LDS stack
-    size_t gstack_cap = 0;        // int32 entries
+    uint64_t nodes_cap() const { return std::min(d_cnodes.cap, d_qnodes.cap); }  // nodes both copies hold
+    arx::DeviceBuf<arx::TriRec> d_tris;
+    arx::DeviceBuf<int32_t> d_gstack;  // global traversal stack for trees deeper than the LDS stack
     bool force_global_stack = false;  // arx_debug_set_trace_path
     bool force_f32_nodes = false;
     unsigned long long* d_hist_ext = nullptr;  // caller-attached (arx_attach_histogram)
-    unsigned long long* hist() const { return d_hist_ext ? d_hist_ext : cur().d_hist; }
+    unsigned long long* hist() const { return d_hist_ext ? d_hist_ext : cur().d_hist.p; }
     // The tree's off-grid flag (a receiver refit or re-quantization put a box outside the quantization
     // grid; its quantized copy then falls back to whole-axis boxes): one word per renderer, outside the
     // per-frame counters the direction pre-pass clears.  Each tree write (ensure_device_scene) runs with
     // a new generation tree_gen and raises the word to it (atomic max) on failure, so the flag reports
     // the tree as last written -- no clear launch, and a later clean write retires an old failure.
-    unsigned int* d_tree_flag = nullptr;
-    unsigned int* h_tree_flag = nullptr;  // pinned
+    arx::DeviceBuf<unsigned int> d_tree_flag;
+    arx::PinnedBuf<unsigned int> h_tree_flag;
     uint32_t tree_gen = 0;
     float debug_refit_pad = 0.0f;  // arx_debug_set_refit_pad: the refit kernel's box padding (0 = automatic)
 
     uint64_t ir_generation = 0;  // bumped whenever the IR changes (finalize_ir, set_ir): streams re-transform
     arx::ConvPlan* conv_live = nullptr;  // mic path plan (block = live block length)
     bool conv_live_ir_dirty = true;
-    double* d_live_in = nullptr;
-    double* d_live_out = nullptr;
+    arx::DeviceBuf<double> d_live_in;   // ir_len
+    arx::DeviceBuf<double> d_live_out;  // 2 * ir_len
 
     arx::ConvPlan* conv = nullptr;
     bool conv_ir_dirty = true;
-    float* d_conv_in = nullptr;
-    float* d_conv_out = nullptr;
-    size_t conv_cap = 0;
+    arx::DeviceBuf<float> d_conv_in;   // the file convolution's staging: n frames in ...
+    arx::DeviceBuf<float> d_conv_out;  // ... and 2 * n out (reserve_conv_staging)
 
     std::vector<arx_stream*> streams;  // live streaming convolutions of this renderer (arx_stream_create)
 
@@ -584,21 +585,26 @@ struct arx_renderer {
     // kernels' scratch, allocated by the frame set's first analysis; queued: the frame that now owns
     // the set was analysed (arx_get_acoustics).
     struct Acoustics {
-        long long* d_edc = nullptr;
-        arx_acoustics* d_res = nullptr;
-        void* d_scratch = nullptr;
+        arx::DeviceBuf<long long> d_edc;
+        arx::DeviceBuf<arx_acoustics> d_res;
+        arx::DeviceBuf<char> d_scratch;
         bool queued = false;
+        void release() {  // with the set, or after a failed first allocation
+            d_edc.release();
+            d_res.release();
+            d_scratch.release();
+            queued = false;
+        }
     };
     bool auto_analyze = false;  // arx_set_auto_analyze
     int32_t scan_shape = 0;     // arx_debug_set_scan_shape (0: the product's)
     struct FrameSet {
         hipStream_t stream = nullptr;
-        unsigned long long* d_hist = nullptr;      // 2*ir_len (own)
-        float* d_ir = nullptr;                     // 2*ir_len: L then R
-        unsigned long long* d_counters = nullptr;  // kCursor + 1 words
-        unsigned long long* h_counters = nullptr;  // pinned, kCounters words
-        void* d_dirs = nullptr;                    // direction pre-pass (float4 per ray of the largest trace call)
-        uint64_t dirs_cap = 0;
+        arx::DeviceBuf<unsigned long long> d_hist;      // 2*ir_len (own)
+        arx::DeviceBuf<float> d_ir;                     // 2*ir_len: L then R
+        arx::DeviceBuf<unsigned long long> d_counters;  // kCursor + 1 words
+        arx::PinnedBuf<unsigned long long> h_counters;  // kCounters words
+        arx::DeviceBuf<float4> d_dirs;                  // direction pre-pass (one per ray of the largest trace call)
         // What d_dirs holds, so a launch of the same seed and range skips the pre-pass's directions
         // (forgotten when the buffer is reallocated): the rays [dirs_begin, dirs_begin + dirs_count)
         // of dirs_seed, in ray order or (dirs_sorted) with the pool's slots ordered for order_key,
@@ -609,15 +615,29 @@ struct arx_renderer {
         arx::OrderKey order_key{};
         // the longest-first pool (made by the set's first measuring launch): the buffer the sort
         // writes (swapped with d_dirs after it), per-slot costs, the sort's bins
-        void* d_dirs_alt = nullptr;
-        unsigned short* d_cost = nullptr;
-        uint32_t* d_order_bins = nullptr;
-        uint64_t order_cap = 0;                    // slots of d_dirs_alt and d_cost
+        arx::DeviceBuf<float4> d_dirs_alt;
+        arx::DeviceBuf<unsigned short> d_cost;
+        arx::DeviceBuf<uint32_t> d_order_bins;          // order_bins_bytes()
         // the path filter's candidate list of this set's replays (two sets replay at once on two
-        // streams): filter_list_cap entries, then the filter blocks' heads (path_filter_list_bytes)
-        void* d_filter_list = nullptr;
-        uint64_t filter_list_cap = 0;
+        // streams): filter_list_rays entries, then the filter blocks' heads (path_filter_list_bytes)
+        arx::DeviceBuf<char> d_filter_list;
+        uint64_t filter_list_rays = 0;
         Acoustics acou;
+        void release() {
+            if (stream) (void)hipStreamDestroy(stream);
+            stream = nullptr;
+            d_hist.release();
+            d_ir.release();
+            d_counters.release();
+            h_counters.release();
+            d_dirs.release();
+            d_dirs_alt.release();
+            d_cost.release();
+            d_order_bins.release();
+            d_filter_list.release();
+            acou.release();
+            *this = FrameSet{};
+        }
     };
     int32_t fif = 1;
     int32_t slot = 0;
@@ -628,13 +648,28 @@ struct arx_renderer {
                ev_scene[kMaxFrames] = {};
     int32_t last_conv = -1, last_reduced = -1, last_scene = -1;
 
-    unsigned long long* d_prof = nullptr;  // per-wave records (profiling builds, ARX_TRACE_PROF)
-    size_t prof_words = 0;
+    arx::DeviceBuf<unsigned long long> d_prof;  // per-wave records (profiling builds, ARX_TRACE_PROF)
+    // The renderer's own buffers; its parts (the scratch structs above, the frame sets) have a release each.
+    void release_buffers() {
+        d_recv_local.release();
+        d_recv_nodes.release();
+        d_recv_levels.release();
+        d_recv_w4.release();
+        d_recv_w4_tris.release();
+        d_cnodes.release();
+        d_qnodes.release();
+        d_tris.release();
+        d_gstack.release();
+        d_live_in.release();
+        d_live_out.release();
+        d_conv_in.release();
+        d_conv_out.release();
+        d_wbuf.release();
+        d_w4f.release();
+        d_prof.release();
+        d_tree_flag.release();
+        h_tree_flag.release();
+    }
     int32_t last_format = 0;  // node format of the last trace launch (arx_stats::trace_format)
     arx_stats stats;
 };
-
-namespace arx {
-// A frame set's analysis buffers released (with the set, or after a failed first allocation).
-void free_acoustics(arx_renderer::Acoustics& a);
-}  // namespace arx
