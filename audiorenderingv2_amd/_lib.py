@@ -216,6 +216,14 @@ SIGNATURES = {
     "arx_debug_directivity_bytes": (C.c_uint64, [C.c_uint64, C.c_int32, C.c_int32]),
     "arx_debug_directivity_planes_made": (C.c_uint64, [_P]),
     "arx_debug_band_histograms": (C.c_int, [_P, _I64, C.c_size_t]),
+    "arx_debug_log10_shared": (C.c_int, [_D, C.c_size_t, _D]),
+    "arx_set_air_absorption": (C.c_int, [_P, _D, C.c_int32]),
+    "arx_air_absorption_bands": (C.c_int32, [_P]),
+    "arx_air_attenuation_host": (C.c_int, [_D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "arx_air_absorption_iso9613": (C.c_int, [C.c_double, C.c_double, C.c_double, _D, C.c_int32, _D]),
+    "arx_debug_air_table": (C.c_int, [_P, C.c_int64, C.c_int64, _F]),
+    "arx_debug_air_bytes": (C.c_uint64, [C.c_int32, C.c_int32]),
+    "arx_debug_air_tables_made": (C.c_uint64, [_P]),
     "arx_debug_set_trace_path": (C.c_int, [_P, C.c_int]),
     "arx_debug_set_refit_pad": (C.c_int, [_P, C.c_float]),
     "arx_debug_check_tree_limits": (C.c_int, [C.c_uint64, C.c_uint64]),

@@ -27,7 +27,7 @@ ARCH = os.environ.get("ARX_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["arx_trace.hip", "arx_replay.hip", "arx_receiver.hip", "arx_conv.hip", "arx_conv_stream.hip", "arx_conv_walk.hip", "arx_band_synth.hip", "arx_directivity.hip", "arx_acoustics.hip", "arx_capi.cpp",
            "arx_scene.cpp", "arx_capi_device_scene.cpp", "arx_capi_trace.cpp", "arx_capi_path_cache.cpp", "arx_capi_listeners.cpp",
-           "arx_capi_bands.cpp", "arx_capi_listener_bands.cpp", "arx_capi_directivity.cpp", "arx_capi_conv.cpp", "arx_group.cpp", "arx_bvh.cpp", "arx_io.cpp", "arx_wide.cpp"]
+           "arx_capi_bands.cpp", "arx_capi_listener_bands.cpp", "arx_capi_directivity.cpp", "arx_capi_air.cpp", "arx_capi_conv.cpp", "arx_group.cpp", "arx_bvh.cpp", "arx_io.cpp", "arx_wide.cpp"]
 # the file / live convolution's kernels and the FFT device code under them: the files conv_source_id hashes
 CONV_KERNEL_FILES = ("arx_conv_fft.hpp", "arx_conv_kernels.hpp")
 # the trace program (trace_kernel, its pre-pass and launchers), the query's device code and the layouts: the

@@ -16,6 +16,7 @@
 // over at the launch boundary.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -98,7 +99,38 @@ __host__ __device__ inline Ranges make_ranges(const int32_t* cnt, int32_t n) {
 
 __host__ __device__ inline double fit_mid(const Ranges& r, int f) { return ((double)r.a[f] + (double)r.b[f]) * 0.5; }
 
-__host__ __device__ inline double level_db(long long e, double dtotal) { return 10.0 * log10((double)e / dtotal); }
+// log10 for the levels, one statement for the host and the device: libm's and the device library's log10 are
+// both within an ulp and not the same function, so a result that is to be the same bytes on both sides cannot go
+// through them.  IEEE f64 add, mul and div only, in the order written, never contracted: x = m * 2^k with m in
+// [sqrt(1/2), sqrt(2)), f = m - 1, s = f / (2 + f), ln(m) = f - f^2/2 + s (f^2/2 + R(s^2)) with the classic
+// degree-7 minimax R, then times 1 / ln(10): the logarithm within 1 ulp and one more rounded product, so within
+// 2 ulp (tests/test_log10_host.py holds it to numpy's over the analysis' argument range).  Every argument here
+// is a ratio of two positive int64, a normal number; anything else (zero, negative, subnormal, inf, NaN) goes
+// to the library's log10.
+__host__ __device__ inline double log10_shared(double x) {
+    const uint64_t bits = __builtin_bit_cast(uint64_t, x);
+    const int ex = (int)((bits >> 52) & 0x7ffu);
+    if ((bits >> 63) != 0 || ex == 0 || ex == 0x7ff) return log10(x);
+    int k = ex - 1023;
+    double m = __builtin_bit_cast(double, (bits & 0x000fffffffffffffull) | 0x3ff0000000000000ull);  // [1, 2)
+    if (m > 1.4142135623730951) {
+        m = m * 0.5;
+        ++k;
+    }
+    const double f = m - 1.0;
+    const double s = f / (2.0 + f);
+    const double z = s * s, w = z * z;
+    const double t1 = w * (3.999999999940941908e-01 + w * (2.222219843214978396e-01 + w * 1.531383769920937332e-01));
+    const double t2 = z * (6.666666666666735130e-01 +
+                           w * (2.857142874366239149e-01 + w * (1.818357216161805012e-01 + w * 1.479819860511658591e-01)));
+    const double R = t2 + t1;
+    const double hfsq = (0.5 * f) * f;
+    const double dk = (double)k;
+    const double ln = dk * 6.93147180369123816490e-01 - ((hfsq - (s * (hfsq + R) + dk * 1.90821492927058770002e-10)) - f);
+    return ln * 4.34294481903251816668e-01;
+}
+
+__host__ __device__ inline double level_db(long long e, double dtotal) { return 10.0 * log10_shared((double)e / dtotal); }
 
 __host__ __device__ inline void acoustics_empty(arx_acoustics* o, double unit) {
     const double nan = __builtin_nan("");
@@ -152,7 +184,7 @@ __host__ __device__ inline void acoustics_finish(arx_acoustics* o, long long tot
             valid |= 1u << 5;
         }
         if (early > 0) {
-            *clarity[w] = late[w] == 0 ? __builtin_inf() : 10.0 * log10((double)early / (double)late[w]);
+            *clarity[w] = late[w] == 0 ? __builtin_inf() : 10.0 * log10_shared((double)early / (double)late[w]);
             valid |= 1u << (3 + w);
         }
     }
@@ -432,6 +464,12 @@ hipError_t launch_acoustics(const AcousticsArgs& a, hipStream_t s) {
 
 extern "C" {
 
+arx_status arx_debug_log10_shared(const double* x, size_t n, double* out) {
+    if (n > 0 && (!x || !out)) return arx::fail(ARX_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (size_t i = 0; i < n; ++i) out[i] = arx::log10_shared(x[i]);
+    return ARX_OK;
+}
+
 arx_status arx_edc_from_histogram(const int64_t* hist, size_t ir_len, int64_t* edc) {
     if (!hist || !edc || ir_len == 0) return arx::fail(ARX_ERR_INVALID_ARGUMENT, "NULL histogram / curve or ir_len == 0");
     unsigned __int128 run = 0;
@@ -472,12 +510,32 @@ arx_status arx_acoustics_from_histogram(const int64_t* left, const int64_t* righ
         for (int p = 0; p < kPreds; ++p)
             while (cnt[p] < n && level_pred(p, e[cnt[p]], lv)) ++cnt[p];
         const Ranges r = make_ranges(cnt, n);
+        // The fits' sums in the device's reduction order (fit_partials_kernel, acoustics_final_kernel): per tile
+        // a strided partial per lane, the lanes' tree, then the tiles in index order -- f64 addition is not
+        // associative, and in this order the same curve gives the device's sums term for term.
         double sxy[3] = {0.0, 0.0, 0.0};
         const double dtotal = (double)total;
-        for (int f = 0; f < 3; ++f) {
-            if (!r.ok[f]) continue;
-            const double mid = fit_mid(r, f);
-            for (int32_t k = r.a[f]; k <= r.b[f]; ++k) sxy[f] += ((double)k - mid) * level_db(e[k], dtotal);
+        const double mid[3] = {fit_mid(r, 0), fit_mid(r, 1), fit_mid(r, 2)};
+        const int64_t tlen = ((int64_t)n + kFitTiles - 1) / kFitTiles;
+        std::vector<double> lanes(3 * (size_t)kFitLanes);
+        for (int tile = 0; tile < kFitTiles; ++tile) {
+            const int64_t k0 = min64((int64_t)n, (int64_t)tile * tlen), k1 = min64((int64_t)n, k0 + tlen);
+            std::fill(lanes.begin(), lanes.end(), 0.0);
+            for (int t = 0; t < kFitLanes; ++t)
+                for (int64_t k = k0 + t; k < k1; k += kFitLanes) {
+                    const long long v = e[(size_t)k];
+                    bool in[3];
+                    for (int f = 0; f < 3; ++f) in[f] = r.ok[f] && k >= r.a[f] && k <= r.b[f];
+                    if ((in[0] || in[1] || in[2]) && v > 0) {
+                        const double y = level_db(v, dtotal);
+                        for (int f = 0; f < 3; ++f)
+                            if (in[f]) lanes[(size_t)f * kFitLanes + t] += ((double)k - mid[f]) * y;
+                    }
+                }
+            for (int stride = kFitLanes / 2; stride > 0; stride >>= 1)
+                for (int t = 0; t < stride; ++t)
+                    for (int f = 0; f < 3; ++f) lanes[(size_t)f * kFitLanes + t] += lanes[(size_t)f * kFitLanes + t + stride];
+            for (int f = 0; f < 3; ++f) sxy[f] += lanes[(size_t)f * kFitLanes];
         }
         unsigned __int128 ts = 0;
         for (int32_t k = r.onset + 1; k < n; ++k) ts += (unsigned __int128)e[k];

@@ -29,8 +29,13 @@ struct BandArgs {
     // rays, or null.  With a plane the launchers take the kernels' DIRECTED instantiations, in which a ray's
     // band b starts from e0 * gain[slot][b]; without one, the instantiations that never read this field.
     const float* gain;
+    // Air absorption (include/arx.h): the attenuation table [bin][band_width(n_bands)], ir_len rows, or null.
+    // Padding columns are 0; a one-coefficient install fills every column.  With a table the launchers take the
+    // depositing kernels' AIR instantiations, in which a receiver deposit of band b in bin k is weighted by
+    // air[k][b]; without one, the instantiations that never read this field.
+    const float* air;
 };
-static_assert(sizeof(BandArgs) == 48, "BandArgs: a kernel parameter behind TraceArgs");
+static_assert(sizeof(BandArgs) == 56, "BandArgs: a kernel parameter behind TraceArgs");
 
 // The scratch of a call for n_bands bands, as byte offsets (every region 16-B aligned): per band a
 // histogram, a counter block, three arx_acoustics and an f32 IR pair (the lefts, then the rights); then one

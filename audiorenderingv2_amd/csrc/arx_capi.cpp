@@ -350,6 +350,7 @@ void arx_destroy(arx_renderer* r) {
     r->walk.release();
     r->bands.release();
     r->directivity.release();
+    r->air.release();
     r->synth.release();
     r->listener_bands.release();
     for (EventRing* ring : {&r->trace_ring, &r->conv_ring, &r->live_ring, &r->analysis_ring}) ring->destroy();

@@ -186,6 +186,7 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     BandState& bs = r->bands;
     if (bs.n_bands < 1) return fail(ARX_ERR_NOT_READY, "arx_set_band_absorption has not been called for this scene");
     if (const arx_status dst = directivity_check_bands(r, bs.n_bands); dst != ARX_OK) return dst;
+    if (const arx_status ast = air_check_bands(r, bs.n_bands); ast != ARX_OK) return ast;
     PathCache& pc = r->path_cache;
     if (pc.mode != 1) return fail(ARX_ERR_NOT_READY, "a band render replays the path cache, which is off");
     const uint64_t N = n_rays(r->cfg);
@@ -223,6 +224,8 @@ arx_status arx_render_bands(arx_renderer* r, float* ir_left, float* ir_right, ar
     ba.n_bands = B;
     // a source pattern: the gain plane of this recording (remade only when stale), and the directed replay
     if ((st = directivity_plane(r, probe.args.dirs, N, B, &ba.gain)) != ARX_OK) return st;
+    // air absorption: the attenuation table (remade only when stale), and the replay that weights its deposits
+    if ((st = air_table(r, B, &ba.air)) != ARX_OK) return st;
     ARX_HIP(launch_band_replay(probe.args, ba, r->stream));
     for (size_t b = 0; b < (size_t)B; ++b)
         if ((st = finalize_and_analyse(r, d_hist + b * 2 * ir_len, d_irl + b * ir_len, d_irr + b * ir_len, d_res + 3 * b,

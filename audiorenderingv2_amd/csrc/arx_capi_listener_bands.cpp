@@ -24,6 +24,8 @@ struct BandCall : ListenerCall {
     arx_listener_band_result* results;
     std::vector<arx_band_result> single;  // per (pose, band) of the one-listener route
     std::vector<float> tmp_ir;            // that route's band IRs when the caller takes only the broadband pair
+    const float* gain = nullptr;          // begin_chunks: the gain plane of a source pattern for this call, or null
+    const float* air = nullptr;           // begin_chunks: air absorption's table for this call, or null
 };
 
 // The one-listener route: the loop's own step, straight into the caller's arrays; it ends synchronised.
@@ -54,16 +56,17 @@ arx_status render_single(ListenerCall& lc, size_t j) {
 // 1. the recording: ordinary launches at the first pose until the cache holds the key's records
 arx_status warm_up(ListenerCall& c) { return record_for_bands(c.r, c.N, &c.poses[0], &c.probe, &c.warm); }
 
-BandArgs band_args(const ListenerCall& c) {
+BandArgs band_args(const ListenerCall& lc) {
+    const BandCall& c = static_cast<const BandCall&>(lc);
     BandArgs ba;
     std::memset(&ba, 0, sizeof(ba));
     ba.table = c.r->bands.d_table.p;
     ba.counters = c.at<unsigned long long>(c.sc.base);
     ba.n_tris = c.r->bands.n_tris;
     ba.n_bands = c.bands;
-    // a source pattern: the plane begin_chunks made for this call's recording
-    const DirectivityState& d = c.r->directivity;
-    ba.gain = d.n_bands >= 1 && d.plane_valid ? d.d_plane.p : nullptr;
+    // a source pattern's plane and air absorption's table, as begin_chunks got them for this call
+    ba.gain = c.gain;
+    ba.air = c.air;
     return ba;
 }
 
@@ -75,8 +78,9 @@ arx_status begin_chunks(ListenerCall& lc) {
     if (c.filters)
         ARX_HIP(hipMemcpyAsync(c.own->d_filters.p, c.filters, (size_t)c.bands * (size_t)c.taps * sizeof(double), hipMemcpyDefault,
                                r->stream));
-    const float* plane = nullptr;  // the gain plane of a source pattern, remade only when stale (band_args reads it)
-    if (const arx_status st = directivity_plane(r, c.probe.args.dirs, c.N, c.bands, &plane); st != ARX_OK) return st;
+    // the gain plane of a source pattern and air absorption's table, each remade only when stale (band_args hands them on)
+    if (const arx_status st = directivity_plane(r, c.probe.args.dirs, c.N, c.bands, &c.gain); st != ARX_OK) return st;
+    if (const arx_status st = air_table(r, c.bands, &c.air); st != ARX_OK) return st;
     ARX_HIP(launch_band_base(c.probe.args, filter_args(c.probe, c.fgrow), band_args(c), c.at<char>(c.sc.counts), r->stream));
     return ARX_OK;
 }
@@ -142,6 +146,7 @@ arx_status arx_render_listener_bands(arx_renderer* r, const arx_listener_pose* p
     if (r->path_cache.mode != 1) return fail(ARX_ERR_NOT_READY, "a band render replays the path cache, which is off");
     const int32_t B = r->bands.n_bands;
     if (const arx_status st = directivity_check_bands(r, B); st != ARX_OK) return st;
+    if (const arx_status st = air_check_bands(r, B); st != ARX_OK) return st;
     BandCall c{{r, &r->listener_bands, poses, n, ir_left, ir_right, acoustics, B, false, ir_left || filters, warm_up, render_single,
                 begin_chunks, replay, filters ? combine : nullptr, write_outputs},
                filters, filters ? taps : 0, bb_left, bb_right, results};

@@ -4,7 +4,8 @@
 // trace, finalize, analysis; arx_capi_path_cache.cpp: the path cache's buffers and launches;
 // arx_capi_listeners.cpp: a batch of listeners and the driver of both batches; arx_capi_bands.cpp: frequency
 // bands; arx_capi_listener_bands.cpp: the bands of a batch of listeners; arx_capi_directivity.cpp: the
-// source's pattern, its orientation and the gain plane; arx_capi_conv.cpp: the
+// source's pattern, its orientation and the gain plane; arx_capi_air.cpp: air absorption's coefficients
+// and attenuation table; arx_capi_conv.cpp: the
 // file, live, streaming and walk-through convolution; arx_group.cpp: ray-sharded multi-GPU groups).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -381,6 +382,32 @@ arx_status directivity_check_bands(const arx_renderer* r, int32_t n_bands);
 // on the renderer's stream: *plane null without a pattern; else the plane, made now if what it was made from
 // has changed.  Nothing of an earlier band call is in flight: each ends synchronised.
 arx_status directivity_plane(arx_renderer* r, const void* dirs, uint64_t n, int32_t n_bands, const float** plane);
+// Air absorption (arx_set_air_absorption, include/arx.h): the coefficients, and the attenuation table
+// [bin][band_width] the band replays' AIR instantiations read at a deposit -- one allocation, kept across
+// calls, freed when it must grow and at arx_destroy; outside the path cache's cap.  The table is made on the
+// host and uploaded by the first band call that needs it, and remade only when the coefficients' generation
+// or the call's band count has moved.  The coefficients survive arx_set_scene and arx_set_band_absorption.
+struct AirState {
+    int32_t n = 0;                // 0: none (the band replays run without the factor); 1 serves every band
+    double alpha[kMaxBands] = {}; // dB per metre
+    DeviceBuf<float> d_table;
+    uint64_t gen = 0;             // changes of the coefficients so far
+    bool table_valid = false;     // d_table holds the table of made_*
+    uint64_t made_gen = 0;
+    int32_t made_bands = 0;
+    uint64_t tables_made = 0;     // uploads so far
+    void release() {
+        d_table.release();
+        n = 0;
+        table_valid = false;
+    }
+};
+// The rule of a band call with coefficients installed: more than one coefficient matches the table's bands.
+arx_status air_check_bands(const arx_renderer* r, int32_t n_bands);
+// The attenuation table for a band call of n_bands bands: *table null without coefficients; else the device
+// table, made now (a host loop and one blocking upload) if what it was made from has changed.  Nothing of an
+// earlier band call is in flight: each ends synchronised.
+arx_status air_table(arx_renderer* r, int32_t n_bands, const float** table);
 // Band synthesis (arx_combine_bands, include/arx.h): one scratch allocation per renderer (the call's inputs,
 // filters and outputs), made by the first call, kept across calls and freed when it must grow and at
 // arx_destroy; outside the path cache's cap.
@@ -535,6 +562,7 @@ struct arx_renderer {
     arx::WalkScratch walk;         // arx_convolute_walk's scratch
     arx::BandState bands;          // arx_render_bands' table and scratch
     arx::DirectivityState directivity;  // the source's pattern, orientation and gain plane
+    arx::AirState air;             // air absorption's coefficients and attenuation table
     arx::SynthScratch synth;       // arx_combine_bands' scratch
     arx::ListenerScratch listener_bands;  // arx_render_listener_bands' scratch
     arx::QGrid qgrid{};

@@ -7,6 +7,8 @@
 // band_cand_multi_kernel do the chunk of listeners for every band at once.  The band kernels' DIRECTED
 // instantiations start a ray's bands from e0 times its row of a gain plane (a source pattern,
 // arx_directivity.hpp); the others are the kernels as they were, and the launchers take them without a plane.
+// Their AIR instantiations weight a receiver deposit by the bin's row of an attenuation table (air absorption,
+// include/arx.h); the launchers take them only with a table.
 //
 // Every query here is the same arithmetic on the same bits as the traced frame's (arx_trace_device.hpp's functions),
 // and each step the kernels share -- the kernel set-up, the record read, the receiver query, a candidate's entry,
@@ -17,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "arx_bands.hpp"
 #include "arx_cand_plan.hpp"
@@ -257,7 +260,31 @@ __device__ __forceinline__ void band_start_directed(const TraceArgs& a, const Ba
     }
 }
 
+// Air absorption (BandArgs::air, include/arx.h): what the bands deposit in bin k, ea[b] = e[b] * att[k][b], one
+// f32 product each, the table's row k in one or two 16-B loads.  Every band's product is formed, live or not (a
+// dead band's is not read): with the products inside the per-band branches the compiler moves the loads in
+// there too, split into dwords, each waited for on its own.  The caller holds 0 <= k < a.ir_len, the table's
+// rows: a dropped hit reads nothing.
 template <int NB>
+__device__ __forceinline__ void band_air_deposits(const BandArgs& ba, int k, const float (&e)[NB], float (&ea)[NB]) {
+    static_assert(NB == 4 || NB == 8, "a table row is one or two 16-B loads");
+    const float4* __restrict__ row = reinterpret_cast<const float4*>(ba.air) + (uint64_t)k * (NB / 4);
+    float4 t[NB / 4];
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) t[q] = row[q];
+#pragma unroll
+    for (int q = 0; q < NB / 4; ++q) {
+        ea[4 * q + 0] = e[4 * q + 0] * t[q].x;
+        ea[4 * q + 1] = e[4 * q + 1] * t[q].y;
+        ea[4 * q + 2] = e[4 * q + 2] * t[q].z;
+        ea[4 * q + 3] = e[4 * q + 3] * t[q].w;
+    }
+}
+
+// AIR: a receiver deposit of band b is e[b] * att[k][b], one f32 product, for both ears at the hit's own bin k
+// (the interaural delay is the head's, not the path's).  The carried e[b] is untouched -- air weights arrivals
+// and never ends a ray -- so the counters and the induction above band_replay_kernel stand as they are.
+template <int NB, bool AIR>
 __device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& ba, const float4* __restrict__ tbase,
                                            RayState& s, const Best& best, float (&e)[NB], uint32_t alive,
                                            uint32_t& rx, uint32_t& miss) {
@@ -315,12 +342,18 @@ __device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& b
             const int kk = (k + a.delay < a.ir_len) ? k + a.delay : k;
             const uint64_t own = (ab == -1.0f) ? 0u : (uint64_t)a.ir_len;
             const uint64_t other = (ab == -1.0f) ? (uint64_t)a.ir_len : 0u;
+            float ea[NB];
+            // k >= 0, for the row as for the histogram below: s.dist is a sum of square roots, so roundf's argument
+            // is >= 0 or NaN, which the conversion takes to 0; +inf converts to INT_MAX and fails k < ir_len
+            if constexpr (AIR) band_air_deposits<NB>(ba, k, e, ea);
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 if ((alive >> b) & 1u) {  // alive holds bits below n_bands only: inside the bands' block
                     unsigned long long* h = ba.hist + (uint64_t)b * 2u * (uint64_t)a.ir_len;
-                    hist_add(h + own, k, e[b], a.inv_unit);
-                    if (!a.is_mono) hist_add(h + other, kk, e[b] * (1.0f - a.hrtf), a.inv_unit);
+                    float eb = e[b];
+                    if constexpr (AIR) eb = ea[b];
+                    hist_add(h + own, k, eb, a.inv_unit);
+                    if (!a.is_mono) hist_add(h + other, kk, eb * (1.0f - a.hrtf), a.inv_unit);
                 }
             }
         }
@@ -344,7 +377,7 @@ __device__ __forceinline__ void band_shade(const TraceArgs& a, const BandArgs& b
 // e[b] never exceeds the recorded ray's energy at the same bounce: a live band's query always has a
 // record.  A lane leaves once no band lives.  Per band the histogram and the three counters are those of
 // replay_kernel on a scene that carries the band's absorption.
-template <int BLOCK, int NB, bool DIRECTED>
+template <int BLOCK, int NB, bool DIRECTED, bool AIR>
 __global__ __launch_bounds__(BLOCK) void band_replay_kernel(TraceArgs a, BandArgs ba) {
     const ReceiverCtx<BLOCK> c = receiver_ctx<BLOCK>(a);
     const int lane = threadIdx.x;
@@ -381,7 +414,7 @@ __global__ __launch_bounds__(BLOCK) void band_replay_kernel(TraceArgs a, BandArg
         }
         receiver_query(c, a, active, s, 0, r, best);
         if (active) {
-            band_shade<NB>(a, ba, c.tbase, s, best, e, alive, rx, miss);
+            band_shade<NB, AIR>(a, ba, c.tbase, s, best, e, alive, rx, miss);
             active = wants_query(a, s);
         }
     }
@@ -909,7 +942,7 @@ __global__ __launch_bounds__(BLOCK) void band_base_kernel(TraceArgs a, FilterArg
 // bits per live band, and per band the queries it took away, from the ray's packed counts.  A ray that does
 // not end contributes nothing, and nothing past its last candidate bounce is read.  Wave-wide like
 // receiver_query.
-template <int BLOCK, int NB, bool DIRECTED>
+template <int BLOCK, int NB, bool DIRECTED, bool AIR>
 __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const TraceArgs& a, const BandArgs& ba,
                                            const FilterCand* __restrict__ list, uint64_t i, bool have, int top,
                                            const uint2* __restrict__ counts, uint32_t (&cut)[NB], uint32_t& rx,
@@ -951,7 +984,7 @@ __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const Tr
             const bool flagged = q + 1u == count && (m & (kFilterMiss | kFilterMarked)) != 0u;
             mask &= mask - 1ull;
             if (best.unit != unit0 || flagged) {
-                band_shade<NB>(a, ba, c.tbase, s, best, e, alive, rx, miss);
+                band_shade<NB, AIR>(a, ba, c.tbase, s, best, e, alive, rx, miss);
                 const uint2 pk = counts[slot];
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
@@ -975,7 +1008,7 @@ __device__ __forceinline__ void band_chain(const ReceiverCtx<BLOCK>& c, const Tr
 // ended rays took away (band_cut_kernel turns them into the frame's count), in words 1 and 2 the frame's
 // receiver hits and misses.  rx and miss are a bit per ray and band: a ballot's population count, summed in
 // scalar registers, lane 0 handing the wave's sum to flush_counters.
-template <int NB, bool DIRECTED>
+template <int NB, bool DIRECTED, bool AIR>
 __global__ __launch_bounds__(64) void band_cand_multi_kernel(TraceArgs a, FilterArgs f, const ListenerEntry* __restrict__ tbl,
                                                              BandArgs ba, const uint2* __restrict__ counts) {
     constexpr int BLOCK = 64;
@@ -1003,7 +1036,7 @@ __global__ __launch_bounds__(64) void band_cand_multi_kernel(TraceArgs a, Filter
         if (base == 0u && lane == 0 && head.x) atomicAdd(e.cand, (unsigned long long)head.x);
         const uint64_t i = fb * kFilterBlock + base + lane;
         uint32_t rx, miss;
-        band_chain<BLOCK, NB, DIRECTED>(c, a, ba, list, i, base + lane < n_cand && i < n, top, counts, cut, rx, miss);
+        band_chain<BLOCK, NB, DIRECTED, AIR>(c, a, ba, list, i, base + lane < n_cand && i < n, top, counts, cut, rx, miss);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             w_rx[b] += (uint32_t)__popcll(__ballot((rx >> b) & 1u));
@@ -1044,6 +1077,31 @@ hipError_t launch_path_replay(const TraceArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// The instantiation of a band kernel that deposits: the row width; without a gain plane and without an
+// attenuation table the ones that never read those fields, with a plane the directed ones, with a table the
+// AIR ones.  f takes the three as integral constants.
+template <class F>
+static void band_instantiation(const BandArgs& b, F&& f) {
+    using W4 = std::integral_constant<int, 4>;
+    using W8 = std::integral_constant<int, 8>;
+    const auto by_air = [&](auto nb, auto directed) {
+        if (b.air)
+            f(nb, directed, std::true_type{});
+        else
+            f(nb, directed, std::false_type{});
+    };
+    const auto by_gain = [&](auto nb) {
+        if (b.gain)
+            by_air(nb, std::true_type{});
+        else
+            by_air(nb, std::false_type{});
+    };
+    if (band_width(b.n_bands) == 4)
+        by_gain(W4{});
+    else
+        by_gain(W8{});
+}
+
 hipError_t launch_band_replay(const TraceArgs& a, const BandArgs& b, hipStream_t s) {
     (void)hipGetLastError();
     if (!trace_can_cache(a, false) || !a.dirs || !a.tris || !a.rec || !b.table || !b.hist || !b.counters || b.n_bands < 1 ||
@@ -1055,16 +1113,9 @@ hipError_t launch_band_replay(const TraceArgs& a, const BandArgs& b, hipStream_t
     constexpr int RB = ARX_REPLAY_BLOCK;
     const uint64_t n_rays = a.ray_end - a.ray_begin;
     const dim3 grid((unsigned)((n_rays + RB - 1) / RB));
-    // without a gain plane the instantiations that never read it; with one, the directed ones
-    const bool w4 = band_width(b.n_bands) == 4;
-    if (!b.gain && w4)
-        hipLaunchKernelGGL((band_replay_kernel<RB, 4, false>), grid, dim3(RB), 0, s, a, b);
-    else if (!b.gain)
-        hipLaunchKernelGGL((band_replay_kernel<RB, 8, false>), grid, dim3(RB), 0, s, a, b);
-    else if (w4)
-        hipLaunchKernelGGL((band_replay_kernel<RB, 4, true>), grid, dim3(RB), 0, s, a, b);
-    else
-        hipLaunchKernelGGL((band_replay_kernel<RB, 8, true>), grid, dim3(RB), 0, s, a, b);
+    band_instantiation(b, [&](auto nb, auto directed, auto air) {
+        hipLaunchKernelGGL((band_replay_kernel<RB, nb(), directed(), air()>), grid, dim3(RB), 0, s, a, b);
+    });
     return hipGetLastError();
 }
 
@@ -1159,15 +1210,9 @@ hipError_t launch_listener_bands_replay(const TraceArgs& a, const FilterArgs& f,
     if (const hipError_t e = launch_listeners_filter(a, f, d_table, listeners, s, &per); e != hipSuccess) return e;
     const dim3 grid((unsigned)per, (unsigned)listeners);
     const uint2* const in = static_cast<const uint2*>(counts);
-    const bool w4 = band_width(b.n_bands) == 4;
-    if (!b.gain && w4)
-        hipLaunchKernelGGL((band_cand_multi_kernel<4, false>), grid, dim3(64), 0, s, a, f, d_table, b, in);
-    else if (!b.gain)
-        hipLaunchKernelGGL((band_cand_multi_kernel<8, false>), grid, dim3(64), 0, s, a, f, d_table, b, in);
-    else if (w4)
-        hipLaunchKernelGGL((band_cand_multi_kernel<4, true>), grid, dim3(64), 0, s, a, f, d_table, b, in);
-    else
-        hipLaunchKernelGGL((band_cand_multi_kernel<8, true>), grid, dim3(64), 0, s, a, f, d_table, b, in);
+    band_instantiation(b, [&](auto nb, auto directed, auto air) {
+        hipLaunchKernelGGL((band_cand_multi_kernel<nb(), directed(), air()>), grid, dim3(64), 0, s, a, f, d_table, b, in);
+    });
     hipLaunchKernelGGL(band_cut_kernel, dim3((unsigned)((listeners * b.n_bands + 255) / 256)), dim3(256), 0, s, d_table,
                        b.counters, b.n_bands, listeners);
     return hipGetLastError();

@@ -171,6 +171,34 @@ class AudioRenderer:
         check(lib().arx_debug_directivity_plane(self._h, first, count, fptr(out)))
         return out
 
+    def set_air_absorption(self, alpha_db_per_m) -> None:
+        """arx_set_air_absorption: the air's loss in dB per metre per band, finite and >= 0 -- one value
+        (serves every band of the table) or one per band; None drops it.  render_bands and
+        render_listener_bands then weight a receiver deposit of band b in bin k by
+        exp(-alpha[b] ln(10) / 10 * k * 343 / sample_rate) (air_attenuation is the table); the energy a
+        ray carries, and so every counter, is unchanged.  air_absorption_iso9613 gives pure-tone values."""
+        if alpha_db_per_m is None:
+            check(lib().arx_set_air_absorption(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(np.atleast_1d(alpha_db_per_m), np.float64)
+        if a.ndim != 1 or a.size < 1:
+            raise ValueError("air absorption: one coefficient, or one per band")
+        check(lib().arx_set_air_absorption(self._h, a.ctypes.data_as(C.POINTER(C.c_double)), a.size))
+
+    @property
+    def n_air_bands(self) -> int:
+        """arx_air_absorption_bands: the coefficients installed, 0 without any."""
+        return int(lib().arx_air_absorption_bands(self._h))
+
+    def air_table(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """arx_debug_air_table: rows [first, first + count) of the device attenuation table, (count, W) f32,
+        a row per IR bin; made now if it is stale.  It needs coefficients, and no recording."""
+        bands = self.n_bands or self.n_air_bands
+        count = self.ir_length - first if count is None else count
+        out = np.zeros((max(count, 0), 4 if bands <= 4 else 8), np.float32)
+        check(lib().arx_debug_air_table(self._h, first, count, fptr(out)))
+        return out
+
     def band_histograms(self) -> np.ndarray:
         """arx_debug_band_histograms: the last render_bands call's raw int64 histograms, (B, 2, ir_len):
         band b's left and right, before finalize."""
@@ -1345,4 +1373,29 @@ def directivity_gains(cube, dirs, orientation=None, width: int | None = None) ->
     out = np.zeros((d.shape[0], max(w, 1)), np.float32)
     check(lib().arx_directivity_gains_host(fptr(c), c.shape[0], c.shape[2], None if m is None else fptr(m), fptr(d),
                                            d.shape[0], w, fptr(out)))
+    return out
+
+
+# -- air absorption (include/arx.h, "Air absorption") -------------------------------------------------------
+def air_absorption_iso9613(freqs_hz, temperature_c: float = 20.0, relative_humidity: float = 50.0,
+                           pressure_kpa: float = 101.325) -> np.ndarray:
+    """arx_air_absorption_iso9613: ISO 9613-1's pure-tone attenuation in dB per metre at each frequency (Hz),
+    for a temperature in [-20, 50] C, a relative humidity in [0, 100] % and a pressure in (0, 200] kPa.  A
+    band takes its centre frequency's value; band-integrated coefficients are the caller's business."""
+    f = np.ascontiguousarray(np.atleast_1d(freqs_hz), np.float64).reshape(-1)
+    out = np.zeros(f.size, np.float64)
+    dp = C.POINTER(C.c_double)
+    check(lib().arx_air_absorption_iso9613(float(temperature_c), float(relative_humidity), float(pressure_kpa),
+                                           f.ctypes.data_as(dp), f.size, out.ctypes.data_as(dp)))
+    return out
+
+
+def air_attenuation(alpha_db_per_m, sample_rate: int, ir_len: int, width: int | None = None) -> np.ndarray:
+    """arx_air_attenuation_host, the table's definition: (ir_len, width) f32 factors, a row per IR bin; one
+    coefficient fills every column, else the columns past the coefficients are 0."""
+    a = np.ascontiguousarray(np.atleast_1d(alpha_db_per_m), np.float64).reshape(-1)
+    w = (4 if a.size <= 4 else 8) if width is None else int(width)
+    out = np.zeros((max(int(ir_len), 0), max(w, 1)), np.float32)
+    check(lib().arx_air_attenuation_host(a.ctypes.data_as(C.POINTER(C.c_double)), a.size, int(sample_rate), int(ir_len), w,
+                                         fptr(out)))
     return out

@@ -275,6 +275,11 @@ arx_status arx_analysis_times(arx_renderer* r, double* ms, size_t n, size_t* n_o
  * sample_rate <= 0); out[c] = channel c. */
 arx_status arx_acoustics_from_histogram(const int64_t* left, const int64_t* right, size_t ir_len,
                                         int32_t sample_rate, double unit, arx_acoustics out[3]);
+/* host only: the log10 the analysis takes for its levels on the device and on the host alike -- IEEE f64 add, mul
+ * and div in a fixed order, within 2 ulp, so that the same decay curve gives the same bytes on both sides (libm's
+ * and the device library's log10 are not the same function).  out[i] for n arguments; an argument that is not a
+ * positive normal number goes to the C library's log10. */
+arx_status arx_debug_log10_shared(const double* x, size_t n, double* out);
 arx_status arx_edc_from_histogram(const int64_t* hist, size_t ir_len, int64_t* edc);
 /* The decay curve's scan kernels: 0 = the product's choice, 1 = one workgroup per channel (one
  * launch), 2 = tiled (tile sums, then an apply that adds up the sums above its tile: two launches;
@@ -1039,6 +1044,86 @@ uint64_t arx_debug_directivity_planes_made(const arx_renderer* r);
 /* the raw fixed-point histograms of the last finished arx_render_bands call, band b's [L | R] at
  * h_out + b * 2 * ir_len, before finalize; capacity in words.  ARX_ERR_NOT_READY before the first call. */
 arx_status arx_debug_band_histograms(arx_renderer* r, int64_t* h_out, size_t capacity);
+
+/* Air absorption: an attenuation per band and path length on the band replays.
+ *
+ * Air attenuates sound with distance, and strongly with frequency: at 20 C and 50 % relative humidity about
+ * 4.7 dB/km at 1 kHz, 30 dB/km at 4 kHz and 105 dB/km at 8 kHz (ISO 9613-1's formula,
+ * arx_air_absorption_iso9613).  A ray's geometry does not depend on its energy, so the path cache's records
+ * serve unchanged: the attenuation is one factor per (band, receiver hit), applied where a band's energy is
+ * deposited.  The coefficients are part of no cache key: installing, changing or dropping them costs one small
+ * host loop, one upload and a replay, never a trace, a recording or a scene build.
+ *
+ * Coefficients: alpha[b], the loss in dB per metre, f64, finite and >= 0; n is 1 (one value serves every band
+ * of the table) or up to ARX_MAX_BANDS.  A NaN, a negative or an infinite value is ARX_ERR_INVALID_ARGUMENT and
+ * arx_last_error() names the band.  A band takes whatever the caller gives it -- its centre frequency's
+ * pure-tone value from arx_air_absorption_iso9613, or a band-integrated coefficient of the caller's own.
+ *
+ * The attenuation is a table per IR bin and band, made on the host in f64 from the renderer's sample_rate and
+ * ir_len (both fixed at arx_create):
+ *   d_k       = ((double)k * 343.0) / (double)sample_rate                  k = 0 .. ir_len-1
+ *   att[k][b] = (float)exp(-((alpha[b] * 0.23025850929940458) * d_k))
+ * d_k is the path length that lands in bin k under the engine's rule k = roundf(dist / 343 * sample_rate), so
+ * the table is off from a hit's true distance by at most half a sample of path (at 0.1 dB/m and 16 kHz about
+ * 0.001 dB).  The speed of sound stays 343 m/s.  alpha >= 0 gives att <= 1: a deposit never grows, and the
+ * int64 histogram's headroom holds as it stands.  att[0][b] is exactly 1.0f, and with alpha[b] == 0 every
+ * entry of band b is exactly 1.0f.  libm's exp is not correctly rounded, so it is the TABLE that is defined on
+ * bits: arx_air_attenuation_host returns it, and the device holds the same bytes (arx_debug_air_table).
+ *
+ * Where it enters: only at a hit on a receiver half with bin k < ir_len, for a live band b --
+ *   ea = e[b] * att[k][b]                                        one f32 product
+ *   own ear:    bin k,  ea
+ *   other ear:  bin kk, ea * (1.0f - hrtf)                        (stereo only; kk = k + delay, folded to k)
+ * Both ears take att at k, not at kk: the interaural delay is the head's, not the path's.  A dropped hit
+ * (k >= ir_len) reads no row.
+ * What stays the same -- the convention: the energy a band carries along its ray is unchanged (e[b], the
+ * e[b] > energy_thres guard, which queries a band runs).  Air absorption weights arrivals and NEVER ends a
+ * ray, so per band the three counters (queries, receiver_hits, misses) are exactly those of the call without
+ * air, and every query a band runs still has a record.
+ *
+ * Who honours it: arx_render_bands and arx_render_listener_bands (its one-listener route and its broadband
+ * pairs included) and what is built on them.  arx_render, arx_render_listeners, the warm launches of the band
+ * calls and renderer groups stay without air.  With no coefficients installed the band calls launch the same
+ * kernel instantiations as before.  At render time more than one coefficient must be as many as the table's
+ * bands (arx_band_count), else ARX_ERR_INVALID_ARGUMENT.  The coefficients survive arx_set_scene and
+ * arx_set_band_absorption; n 0 drops them.  A call that fails with ARX_ERR_INVALID_ARGUMENT or
+ * ARX_ERR_NOT_READY changes nothing.  Coefficients and a source pattern may be installed together: the pattern
+ * sets the energy a band starts from, the air factor applies at the deposit.
+ *
+ * The device table att[bin][W] (W = 4 for up to four bands, 8 beyond; the padding 0, or every column filled
+ * for one coefficient) is made by the first band call that needs it and remade only when the coefficients or
+ * the call's band count have changed since.  Memory, OUTSIDE arx_debug_set_path_cache's max_bytes
+ * (arx_debug_air_bytes): ir_len x W x 4 B, 3 MB at 96 000 bins and W = 8; kept across calls, freed when it must
+ * grow and at arx_destroy.  Out of scope: groups, the C++ shim, app.py modes, air absorption on arx_render and
+ * arx_render_listeners, a temperature-dependent speed of sound (the distance limit, and so the recording,
+ * depends on it), per-hit instead of per-bin attenuation, air absorption as a reason to end a ray. */
+arx_status arx_set_air_absorption(arx_renderer* r, const double* alpha_db_per_m, int32_t n); /* n 0 drops */
+/* coefficients installed: 0 without any (and for a NULL r) */
+int32_t arx_air_absorption_bands(const arx_renderer* r);
+/* host only, the table's definition: out[k * width + b]; width 4 or 8 and at least n; n == 1 fills all `width`
+ * columns, else the columns at and past n are 0; sample_rate and ir_len positive.  The coefficients are checked
+ * as the setter checks them. */
+arx_status arx_air_attenuation_host(const double* alpha_db_per_m, int32_t n, int32_t sample_rate, int32_t ir_len,
+                                    int32_t width, float* out);
+/* host only: ISO 9613-1's pure-tone attenuation in dB/m at each of n frequencies.  With T = temperature_c +
+ * 273.15, T0 = 293.15, T01 = 273.16, p = pressure_kpa / 101.325, f in Hz:
+ *   C   = -6.8346 (T01/T)^1.261 + 4.6151;   h = relative_humidity_percent 10^C / p
+ *   frO = p (24 + 4.04e4 h (0.02 + h) / (0.391 + h))
+ *   frN = p (T/T0)^(-1/2) (9 + 280 h exp(-4.170 ((T/T0)^(-1/3) - 1)))
+ *   alpha = 8.686 f^2 (1.84e-11 / p (T/T0)^(1/2) + (T/T0)^(-5/2) (0.01275 exp(-2239.1/T) / (frO + f^2/frO)
+ *                                                                + 0.1068 exp(-3352.0/T) / (frN + f^2/frN)))
+ * Accepted: temperature in [-20, 50] C, humidity in [0, 100] %, pressure in (0, 200] kPa, f > 0; anything else,
+ * or non-finite, is ARX_ERR_INVALID_ARGUMENT. */
+arx_status arx_air_absorption_iso9613(double temperature_c, double relative_humidity_percent, double pressure_kpa,
+                                      const double* freq_hz, int32_t n, double* alpha_db_per_m);
+/* rows [first_bin, first_bin + count) of the device table (W floats each, W from the band count the next band
+ * call runs with: the table's, or the coefficients' without a band table), made now if it is stale.  The table
+ * depends on no recording, so none is needed; ARX_ERR_NOT_READY without coefficients. */
+arx_status arx_debug_air_table(arx_renderer* r, int64_t first_bin, int64_t count, float* h_out);
+/* host only: the formula above (0 for n_bands outside 1..ARX_MAX_BANDS or a negative ir_len) */
+uint64_t arx_debug_air_bytes(int32_t ir_len, int32_t n_bands);
+/* attenuation tables made so far (uploads) */
+uint64_t arx_debug_air_tables_made(const arx_renderer* r);
 
 /* Walk-through convolution: one signal against a per-block IR schedule, in one call.
  *
